@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- energy+force throughput of the GotenNet hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--lmax 2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--lmax 2] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one energy+force evaluation (representation forward, Atomwise head,
@@ -14,8 +14,13 @@ timed region.  N > 1: molecules are sharded by batch index (rank r owns molecule
 [128 r, 128 (r+1))), weights replicated, ONE RCCL all-reduce per step on the
 zero-padded energy vector; forces stay shard-local (weak scaling).
 
-Prints one JSON line (rank 0).  `roofline` is measured live with HIP events around
-every launch of the dominant kernel inside the timed region; `cpu_baseline` times the
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times exactly K steps and
+prints the headline (`value`, `ms_per_step`, ...); `--dump-outputs DIR` also writes the
+energies and forces of the last timed step as DIR/energy.npy and DIR/forces.npy.
+
+`--full` adds everything else: `roofline` measured live with HIP events around every
+launch of the dominant kernel inside the timed region (and rocprofv3 traffic sub-runs),
+the side workloads and configurations under `also`, and `cpu_baseline`, which times the
 CPU oracle (oracle/, a restatement pinned to the reference's golden vectors) on a
 bounded sample of the same workload on this box's host cores.
 """
@@ -148,8 +153,8 @@ def compact_line(full):
                                 "value_one_at_a_time", "ms_per_batch_one_at_a_time", "roofline_target",
                                 "lanes_consistent", "lanes_fallback")
            if k in full and not (k == "rank_ms_per_step" and full[k] is None)}
-    out["roofline"] = _roof_compact(full.get("roofline"))
-    if out["roofline"] is not None:
+    if full.get("roofline"):                         # (a plain run measures no roofline)
+        out["roofline"] = _roof_compact(full["roofline"])
         live = str((full.get("roofline") or {}).get("traffic_source", "")).startswith("measured in this run")
         out["roofline"]["traffic_source"] = ("live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE sub-runs of this bench (2 x FETCH + WRITE)"
                                              if live else "committed profiles/pmc_traffic.json (rocprofv3 --pmc; FETCH_SIZE x2 + WRITE_SIZE)")
@@ -243,7 +248,15 @@ def main():
     ap.add_argument("--selftest-dist", action="store_true",
                     help="CPU-only check of the launch / rendezvous / shard / all-reduce / JSON path (gloo backend, the step "
                          "replaced by a per-molecule checksum of the synthetic inputs); no kernel runs, no throughput claim")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel breakdown and rooflines, live PMC traffic, the side "
+                         "workloads / precisions / configurations, the CPU baselines and the full record; the --no-* options "
+                         "and --breakdown select within it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the energies [B, 1] and forces [N, 3] of the last timed step (rank 0) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.breakdown and not a.full:
+        ap.error("--breakdown is part of --full")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(a)                      # plain `python bench.py --gpus N`: spawn one rank per GPU
     worker(a)
@@ -330,27 +343,36 @@ def worker(a):
         dist.init_process_group("nccl", device_id=dev)
 
     from gotennet_amd import engine
-    if world == 1 and rank == 0 and not a.no_live_traffic and not a.force_dist:
+    if a.full and world == 1 and rank == 0 and not a.no_live_traffic and not a.force_dist:
         # BEFORE this process touches the GPU's counters itself: the sub-runs profile the same headline workload
         lt = live_traffic(a)
         if lt:
             LIVE_TRAFFIC.update(lt, _key=(a.workload, a.batch, a.lmax))
-    res = measure(a, a.workload, a.batch, a.lmax, a.steps, a.warmup, rank, world, dev, dist)
+    res = measure(a, a.workload, a.batch, a.lmax, a.steps, a.warmup, rank, world, dev, dist, keep_outputs=True)
     one_at_a_time = None
-    if world > 1 and res["lanes"] > 1:
-        # N > 1: the same K steps one at a time as well (both figures in the record).  Should the laned run have lost a
+    lanes_lost = not res["lanes_ok"] or res["n_ranks_seen"] != world
+    if world > 1 and res["lanes"] > 1 and (a.full or lanes_lost):
+        # N > 1: the same K steps one at a time as well (both figures in the record, --full).  Should the laned run have lost a
         # shard or a rank (verdict shared by all ranks: an all-reduced flag), the one-at-a-time run IS the headline.
         import copy
         a1 = copy.copy(a)
         a1.lanes = 1
-        res1 = measure(a1, a.workload, a.batch, a.lmax, a.steps, a.warmup, rank, world, dev, dist)
+        res1 = measure(a1, a.workload, a.batch, a.lmax, a.steps, a.warmup, rank, world, dev, dist, keep_outputs=True)
         if rank == 0:
             one_at_a_time = {"value": res1["out"]["value"], "ms_per_batch": res1["out"]["ms_per_step"]}
-        if not res["lanes_ok"] or res["n_ranks_seen"] != world:
+        if lanes_lost:
             if rank == 0:
                 res1["out"]["lanes_fallback"] = (f"{res['lanes']} batches in flight failed the shard check "
                                                  f"(value {res['out']['value']}): headline = one step at a time")
             res = res1
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res["outputs"])
+    if not a.full:                                  # a plain run: the headline line and nothing else
+        if rank == 0:
+            os.write(JSON_FD, (compact_line(res["out"]) + "\n").encode())
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     sides = world == 1                              # side measurements only on the single-GPU line
     side = lat = lat_batch = None
     wl = {}
@@ -435,6 +457,16 @@ def worker(a):
         emit(out, a.full_json)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, outputs):
+    """`--dump-outputs`: what the timed path returned in its last step, one float32 / float64 .npy file per array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float32)
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def in_flight(a, rep, head, dev, lmax, steps=20, lanes=2):
@@ -556,7 +588,10 @@ def algorithmic_bytes_message_backward_first(N, E, F, ND, D, H):
     return edge + node
 
 
-def measure(a, workload, B, lmax, steps, warmup, rank, world, dev, dist):
+def measure(a, workload, B, lmax, steps, warmup, rank, world, dev, dist, keep_outputs=False):
+    """K timed steps of the energy+force path.  ``a.full``: an untimed per-kernel breakdown step first and HIP-event brackets
+    on the last timed steps (the roofline records); otherwise the timed steps carry no instrumentation.  ``keep_outputs``:
+    a host copy of the last step's energies and forces for ``--dump-outputs``."""
     import gotennet_amd
     from gotennet_amd import _lib, synthetic
     from gotennet_amd.graph import distance
@@ -622,7 +657,7 @@ def measure(a, workload, B, lmax, steps, warmup, rank, world, dev, dist):
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- untimed: warm-up + per-kernel breakdown to pick the dominant kernel ----------
+    # ---- untimed: warm-up (+ with --full, a per-kernel breakdown to pick the dominant kernel) ----------
     for _ in range(max(warmup, 1)):
         step()
     if fl is not None:
@@ -630,40 +665,42 @@ def measure(a, workload, B, lmax, steps, warmup, rank, world, dev, dist):
             step_lane()
     fence()
     replay = step_fn.replay
-    kt = KernelTimer()
-    _lib.TIMER = kt
-    step_fn.replay = False                                 # per-launch events need the eager launches
-    step()
-    torch.cuda.synchronize()
-    step_fn.replay = replay
-    _lib.TIMER = None
-    tot, cnt = kt.summary()
-    from gotennet_amd import engine as _eng
-    zero_first = _eng.zero_X_in(rep.config(), 0)
-    fam = {}
-    for tag, t in tot.items():
-        fam[family(tag)] = fam.get(family(tag), 0.0) + t
-    dominant = max(fam, key=fam.get)               # kernel family with the largest share of the step
-    stage_tags = {t for t in tot if t in MSG_STAGE}
-    if a.breakdown and rank == 0:
-        ssum = sum(tot.values())
-        print(f"# {workload} b={B} lmax={lmax} mode={_engine_mode()}: per-kernel HIP-event breakdown of one step "
-              f"({ssum:.3f} ms of events)", file=sys.stderr)
-        for tag in sorted(tot, key=tot.get, reverse=True):
-            print(f"  {tag:42s} {tot[tag]:8.3f} ms/step {cnt[tag]:3d} calls {1e3 * tot[tag] / cnt[tag]:8.1f} us/call "
-                  f"{100 * tot[tag] / ssum:5.1f}%", file=sys.stderr)
+    if a.full:
+        kt = KernelTimer()
+        _lib.TIMER = kt
+        step_fn.replay = False                             # per-launch events need the eager launches
+        step()
+        torch.cuda.synchronize()
+        step_fn.replay = replay
+        _lib.TIMER = None
+        tot, cnt = kt.summary()
+        from gotennet_amd import engine as _eng
+        zero_first = _eng.zero_X_in(rep.config(), 0)
+        fam = {}
+        for tag, t in tot.items():
+            fam[family(tag)] = fam.get(family(tag), 0.0) + t
+        dominant = max(fam, key=fam.get)           # kernel family with the largest share of the step
+        stage_tags = {t for t in tot if t in MSG_STAGE}
+        if a.breakdown and rank == 0:
+            ssum = sum(tot.values())
+            print(f"# {workload} b={B} lmax={lmax} mode={_engine_mode()}: per-kernel HIP-event breakdown of one step "
+                  f"({ssum:.3f} ms of events)", file=sys.stderr)
+            for tag in sorted(tot, key=tot.get, reverse=True):
+                print(f"  {tag:42s} {tot[tag]:8.3f} ms/step {cnt[tag]:3d} calls {1e3 * tot[tag] / cnt[tag]:8.1f} us/call "
+                      f"{100 * tot[tag] / ssum:5.1f}%", file=sys.stderr)
+        # HIP events bracket the message-stage / HTR / message-backward launches on the LAST `ev_steps` timed steps and the
+        # projection launches on the last one only: bracketing those ~23 launches on every step cost 0.115 ms/step (8.11 vs
+        # 7.995 ms, same process), i.e. the measurement perturbed `value` by 1.4 %; the per-launch averages are the same
+        # either way (111.1 us for the message stage in both).
+        dom_tags = {t for t in tot if family(t) == dominant}
+        always = stage_tags | {HTR_TAG, MSGB_TAG, "gn_htr_backward"}
 
-    # ---- timed region: exactly K steps.  HIP events bracket the message-stage / HTR / message-backward launches on the
-    # LAST `ev_steps` timed steps and the projection launches on the last one only: bracketing those ~23 launches on
-    # every step cost 0.115 ms/step (8.11 vs 7.995 ms, same process), i.e. the measurement perturbed `value` by 1.4 %;
-    # the per-launch averages are the same either way (111.1 us for the message stage in both).
-    dom_tags = {t for t in tot if family(t) == dominant}
-    always = stage_tags | {HTR_TAG, MSGB_TAG, "gn_htr_backward"}
+    # ---- timed region: exactly K steps (with --full, the last `ev_steps` of them under HIP-event brackets)
     # (with batches in flight the bracketed steps run alone, i.e. slower than the rest: ONE such step -- 6 launches per stage,
     #  68 projection launches -- instead of three)
-    ev_steps = min(1 if lanes > 1 else 3, steps)
+    ev_steps = min(1 if lanes > 1 else 3, steps) if a.full else 0
     kt = KernelTimer(wanted=set())
-    _lib.TIMER = kt
+    _lib.TIMER = kt if a.full else None
     lane_last = None
     fence()
     t0 = time.perf_counter()
@@ -695,12 +732,15 @@ def measure(a, workload, B, lmax, steps, warmup, rank, world, dev, dist):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     assert torch.isfinite(e).all() and torch.isfinite(f).all()
-    # what the collective produced: every rank's shard present exactly once in the all-reduced vector
+    outputs = {"energy": e.detach().cpu().numpy(), "forces": f.detach().cpu().numpy()} if keep_outputs and rank == 0 else None
+    # what the collective produced: every rank's shard present exactly once in the all-reduced vector (the last timed step's
+    # vector: e_all when step() ran it, the reducer's buffer of its collective when it ran in a lane)
     n_ranks_seen = dist.get_world_size() if dist is not None else 1
-    e_vec = e_all if dist is not None else e[:, 0]
+    e_red = lane_last[1] if (lane_last is not None and not ev_steps) else e_all
+    e_vec = e_red if dist is not None else e[:, 0]
     lanes_ok = True
     if dist is not None:
-        assert torch.equal(e_all[rank * B:(rank + 1) * B], e[:, 0]), "all-reduced energy vector lost this rank's shard"
+        assert torch.equal(e_red[rank * B:(rank + 1) * B], e[:, 0]), "all-reduced energy vector lost this rank's shard"
         # the same for the LAST laned step (its collective left from the reducer's communication stream), and the count of
         # non-zero entries of its vector = every rank's shard arrived in THAT collective; the verdict is shared by all ranks
         ok = 1.0
@@ -876,13 +916,19 @@ def measure(a, workload, B, lmax, steps, warmup, rank, world, dev, dist):
                        "global_batch": B * world, "parallelism": f"dp{world} (molecule shards, 1 all-reduce)"},
             "n_ranks_seen": n_ranks_seen, "energy_vector_len": int(e_vec.numel()), "energy_checksum": energy_checksum,
             "rank_ms_per_step": rank_ms,
-            "launch_mode": (f"hipGraph replay of the static-topology step ({steps - ev_steps} of {steps} timed steps; the last "
-                            f"{ev_steps} run eagerly under HIP-event brackets)" if replayed else
+            "launch_mode": ((f"hipGraph replay of the static-topology step ({steps - ev_steps} of {steps} timed steps; the last "
+                             f"{ev_steps} run eagerly under HIP-event brackets)" if ev_steps else
+                             "hipGraph replay of the static-topology step (every timed step)") if replayed else
                             (("eager launches; fresh batch every step (CSR / CSC / out-degree / molecule offsets rebuilt inside the timed step)"
                               if fresh else "eager launches; static topology (index arrays cached across steps)")
-                             + (f"; {lanes} batches in flight on {lanes} HIP streams for the first {steps - ev_steps} timed steps, the last "
-                                f"{ev_steps} (HIP-event brackets) one at a time" if lanes > 1 else "; one step at a time"))),
+                             + ((f"; {lanes} batches in flight on {lanes} HIP streams for the first {steps - ev_steps} timed steps, the last "
+                                 f"{ev_steps} (HIP-event brackets) one at a time" if ev_steps else
+                                 f"; {lanes} batches in flight on {lanes} HIP streams for every timed step")
+                                if lanes > 1 else "; one step at a time"))),
             "batches_in_flight": lanes, "lanes_consistent": lanes_ok,
+        }
+    if out is not None and a.full:
+        out.update({
             "roofline": roof_gemm_family() if dominant == "gn_gemm" else
             (roof_message() if dominant in MSG_STAGE else roof_other(dominant)),
             "roofline_gather_scatter": roof_message(),
@@ -890,7 +936,7 @@ def measure(a, workload, B, lmax, steps, warmup, rank, world, dev, dist):
             "roofline_message_backward": roof_msg_backward(),
             "roofline_htr_backward": roof_htr_backward(),
             "roofline_gated_gemm": roof_gated_gemm(),
-        }
+        })
         if LIVE_TRAFFIC.get("_key") == (workload, B, lmax) and "mfma_busy" in LIVE_TRAFFIC and out["roofline"].get("bound") == "mfma":
             out["roofline"]["mfma_busy"] = LIVE_TRAFFIC["mfma_busy"]
         # the stage fractions again INSIDE `roofline` (a consumer that keeps only that object still sees them)
@@ -904,7 +950,8 @@ def measure(a, workload, B, lmax, steps, warmup, rank, world, dev, dist):
             "2 x FETCH + WRITE KiB per the gfx950 note), per-launch averages" if live else
             "committed rocprofv3 --pmc passes of this workload (profiles/pmc_traffic.json, FETCH_SIZE x2 + WRITE_SIZE per "
             "the gfx950 note), not re-measured in this run")
-    return {"out": out, "rep": rep, "head": head, "lanes": lanes, "lanes_ok": lanes_ok, "n_ranks_seen": n_ranks_seen}
+    return {"out": out, "rep": rep, "head": head, "lanes": lanes, "lanes_ok": lanes_ok, "n_ranks_seen": n_ranks_seen,
+            "outputs": outputs}
 
 
 #: HBM bytes per launch measured IN THIS RUN (tag -> bytes), filled by live_traffic() before the headline record is built
@@ -971,7 +1018,8 @@ def live_traffic(a):
                 cmd = [exe, "--kernel-trace", "--pmc", *counter.split(), "-d", out, "-o", "r", "--", sys.executable,
                        os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", str(a.batch),
                        "--lmax", str(a.lmax), "--workload", a.workload, "--no-lmax4", "--no-split", "--no-graph",
-                       "--no-workloads", "--no-cpu-baseline", "--no-forward-only", "--no-live-traffic", "--no-static", "--lanes", "1"]
+                       "--no-workloads", "--no-cpu-baseline", "--no-forward-only", "--no-live-traffic", "--no-static", "--lanes", "1",
+                       "--full"]
                 env = dict(os.environ, TMPDIR="/tmp")
                 subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                                timeout=240, check=True)

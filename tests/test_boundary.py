@@ -772,6 +772,33 @@ def test_bench_one_rank_rccl_path():
     assert dist_["rank_ms_per_step"] and len(dist_["rank_ms_per_step"]) == 1
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps, prints the headline keys and none of the --full records, and
+    `--dump-outputs` writes the last step's energies [B, 1] and forces [N, 3]."""
+    import json
+    import subprocess
+    import sys
+    from gotennet_amd import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in out, k
+    for k in ("roofline", "also", "cpu_baseline", "full_record"):
+        assert k not in out, k
+    pos, _, _ = synthetic.make_batch("rmd17_aspirin", 8, seed=0)
+    e, f = np.load(tmp_path / "energy.npy"), np.load(tmp_path / "forces.npy")
+    assert e.shape == (8, 1) and f.shape == (pos.shape[0], 3)
+    assert e.dtype == np.float32 and f.dtype == np.float32
+    assert np.isfinite(e).all() and np.isfinite(f).all()
+    assert abs(float(e.astype(np.float64).sum()) - out["energy_checksum"]) <= 1e-6 * max(1.0, abs(out["energy_checksum"]))
+
+
 # --------------------------------------------------------------------------------------------------- AtomwiseV3
 def _head_kat_v3():
     k = np.load(os.path.join(GOLDEN_DIR, "kat_head_v3.npz"))

@@ -615,6 +615,37 @@ def qm9_heads_kat():
     print("kat_qm9_heads written:", sorted(k for k in out if "/" in k)[:6], "...", float(r1["property"][0]), float(r3["property"][0]))
 
 
+#: tests/test_oracle_vs_reference_live.py: (lmax, sep_dir = sep_tensor, scale_edge); weights seeded_fill(100 + lmax)
+ORACLE_FP64_CASES = [(1, False, True), (2, True, False), (3, True, True), (4, True, False)]
+
+
+def oracle_fp64_kat():
+    """The reference forward in fp64 on small seeded models (F = 32, L = 3, lmax 1..4) and two 7-atom molecules: inputs and
+    (h, X) only -- the weights are rebuilt from tests.golden_util.seeded_fill, the edges from oracle.distance."""
+    sys.path.insert(0, ROOT)
+    from oracle import gotennet_oracle as orc
+    from tests.golden_util import seeded_fill
+    out = {}
+    for lmax, sep, scale in ORACLE_FP64_CASES:
+        hp = dict(n_atom_basis=32, n_interactions=3, n_rbf=8, lmax=lmax, num_heads=4, scale_edge=scale,
+                  sep_dir=sep, sep_tensor=sep, max_z=12)
+        net = ref.GotenNet(cutoff_fn=ref_layers.CosineCutoff(5.0), **hp)
+        seeded_fill(net, 100 + lmax)
+        net = net.double().eval()
+        g = torch.Generator().manual_seed(lmax)
+        pos = torch.cat([torch.rand((7, 3), generator=g, dtype=torch.float64) * 3.0 + 10.0 * b for b in range(2)])
+        batch = torch.arange(2).repeat_interleave(7)
+        z = torch.randint(1, 9, (14,), generator=g)
+        ei, w, vec = orc.distance(pos, batch, 5.0)
+        with torch.no_grad():
+            h, X = net(z, ei, w.clone(), vec.clone())          # the reference normalises edge_vec in place
+        p = f"l{lmax}/"
+        out.update({p + "pos": pos.numpy(), p + "batch": batch.numpy(), p + "z": z.numpy(), p + "edge_index": ei.numpy(),
+                    p + "h": h.numpy(), p + "X": X.numpy()})
+    np.savez_compressed(os.path.join(OUT, "kat_oracle_fp64.npz"), **out)
+    print("kat_oracle_fp64 written:", sorted(out)[:6], "...")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(1)  # deterministic reduction order for the goldens
     only = sys.argv[1:]                    # optional: names of the fixtures to (re)generate
@@ -637,3 +668,5 @@ if __name__ == "__main__":
         qm9_heads_kat()
     if not only or "kat_head" in only:
         head_kat()
+    if not only or "kat_oracle_fp64" in only:
+        oracle_fp64_kat()

@@ -15,9 +15,10 @@ if [ "$1" != "run" ]; then
   ls gotennet_amd/sweep | wc -l
 else
   cp gotennet_amd/libgotennet_hip.so /tmp/base.so
+  BD=$(mktemp)
   one() {
-    python bench.py --no-cpu-baseline --no-split --no-graph --breakdown 2>gpurun_out/bd.txt | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-12s lmax2 %.3f ms   lmax4 %.3f ms' % ('$1', d['ms_per_step'], d['also']['lmax4']['ms_per_step']))"
-    grep -E "message_backward|htr_backward|message_aggregate|htr_edge|attn_softmax" gpurun_out/bd.txt | awk '{printf "      %-24s %s us\n", $1, $6}'
+    python bench.py --full --no-cpu-baseline --no-split --no-graph --breakdown 2>"$BD" | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-12s lmax2 %.3f ms   lmax4 %.3f ms' % ('$1', d['ms_per_step'], d['also']['lmax4']['ms_per_step']))"
+    grep -E "message_backward|htr_backward|message_aggregate|htr_edge|attn_softmax" "$BD" | awk '{printf "      %-24s %s us\n", $1, $6}'
   }
   one base
   for v in $VARIANTS; do
