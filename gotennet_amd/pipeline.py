@@ -203,6 +203,8 @@ class InFlight:
         self._k, self._seen = 0, set()
         self._pending = []                           # tensors returned since the last wait()
         self._pack = None                            # the weight pack the lanes were last fed with (kept alive across a rebuild)
+        self._gen = 0                                # bumped with every new pack: the cold-call key (an id() of a freed pack
+                                                     # can come back for a later one)
 
     @staticmethod
     def _tensors(objs):
@@ -226,7 +228,8 @@ class InFlight:
             # its blocks are not handed to the rebuild above or to anything after it while they are in use
             self.wait()
             self._pack = pw
-        pack_id = id(pw)
+            self._gen += 1
+            self._seen.clear()                       # keys of earlier packs can never match again
         st.wait_stream(torch.cuda.current_stream(st.device))
         for t in self._tensors(list(args) + list(kw.values())):
             if t.is_cuda:
@@ -234,7 +237,7 @@ class InFlight:
         # The first call of a kind (with / without forces) builds lazily cached operands that ALL lanes share -- packed
         # weights, their fp16 planes, the transposes of the backward -- on THIS lane's stream: it runs alone, fenced against
         # the other lanes on both sides.  Later calls find the caches filled and overlap freely.
-        kind = (bool(kw.get("forces", True)), pack_id)       # (a weight update makes a new pack: cold again)
+        kind = (bool(kw.get("forces", True)), self._gen)     # (a weight update makes a new pack: cold again)
         cold = kind not in self._seen
         if cold:
             for other in self.streams:

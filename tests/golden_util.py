@@ -70,3 +70,87 @@ def rel_err(a, b):
     a = a.double()
     b = b.double()
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-300))
+
+
+# ------------------------------------------------------------------------------------ per-molecule checks of full batches
+def molecule_rows(batch, m):
+    """Row slice of molecule ``m`` in a molecule-sorted batch vector (molecules are contiguous row ranges)."""
+    b = batch.detach().cpu()
+    lo = int(torch.searchsorted(b, torch.tensor(m)))
+    hi = int(torch.searchsorted(b, torch.tensor(m), right=True))
+    return slice(lo, hi)
+
+
+def take_molecule(pos, batch, z, m):
+    """Molecule ``m`` alone: (pos, batch of zeros, z, its row slice in the full batch)."""
+    rows = molecule_rows(batch, m)
+    n = rows.stop - rows.start
+    return pos[rows], torch.zeros(n, dtype=batch.dtype, device=batch.device), z[rows], rows
+
+
+def group_rel_err(a, b, groups):
+    """Per-group max-norm relative error: for every index ``g`` of ``groups``, max|a[g] - b[g]| / max|b[g]| -- a group is
+    measured against its OWN largest value, not the largest value of the whole tensor.  Returns the list of errors."""
+    return [rel_err(a[g], b[g]) for g in groups]
+
+
+def degree_blocks(lmax):
+    """Index of each degree block l = 1..lmax of X [N, D, F] (rows l^2 - 1 .. (l+1)^2 - 2 of the D axis)."""
+    return [(slice(None), slice(l * l - 1, (l + 1) ** 2 - 1)) for l in range(1, lmax + 1)]
+
+
+def weights_key(*state_dicts):
+    """Fingerprint of the weights (names, shapes, bytes): part of a cache key of results computed from them."""
+    import hashlib
+    hsh = hashlib.sha1()
+    for sd in state_dicts:
+        for k in sorted(sd):
+            v = sd[k].detach().cpu().contiguous()
+            hsh.update(f"{k}:{tuple(v.shape)}:{v.dtype}".encode())
+            hsh.update(v.numpy().tobytes())
+    return hsh.hexdigest()
+
+
+_ORACLE_CACHE = {}
+
+
+def oracle_molecule(cfg, sd, head_sd, pos, batch, z, m, forces=True, upstream=None, max_num_neighbors=32):
+    """The fp64 oracle (oracle/gotennet_oracle.py) on molecule ``m`` of a batch, run on that molecule ALONE: molecules do not
+    interact, so this is exactly what a batched run must return for it.  -> dict of fp64 CPU tensors: h, X, energy [1, 1],
+    energy_mass (the sum of the molecule's |atomic energies|: the scale of the rounding of a sum), and with ``forces`` the
+    forces; with ``upstream = (wh, wX)`` (full-batch per-atom weights of h and X) also
+    ``pos_grad_h`` = d sum(wh * h) / d pos and ``pos_grad_X`` = d sum(wX * X) / d pos of the molecule's atoms.
+
+    Cached per (config, weights, inputs, molecule, request) for the life of the process: one oracle run per molecule is
+    shared by every arithmetic and every test that asks for it."""
+    from oracle import gotennet_oracle as orc
+    wkey = weights_key(sd, head_sd)
+    p, b, zz, rows = take_molecule(pos.detach().cpu(), batch.detach().cpu(), z.detach().cpu(), m)
+    ukey = None if upstream is None else weights_key({"wh": upstream[0], "wX": upstream[1]})
+    key = (json.dumps(cfg, sort_keys=True), wkey, weights_key({"pos": p, "z": zz}), m, bool(forces), ukey, max_num_neighbors)
+    if key in _ORACLE_CACHE:
+        return _ORACLE_CACHE[key]
+    d64 = lambda s: {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu()) for k, v in s.items()}
+    sd64, hsd64 = d64(sd), d64(head_sd)
+    grad = forces or upstream is not None
+    old_threads = torch.get_num_threads()
+    torch.set_num_threads(min(8, os.cpu_count() or 1))
+    try:
+        with torch.enable_grad() if grad else torch.no_grad():
+            p64 = p.double().clone().requires_grad_(grad)
+            ei, w, vec = orc.distance(p64, b, cfg["cutoff"], max_num_neighbors)
+            h, X = orc.gotennet_forward(sd64, cfg, zz, ei, w, vec)
+            e = orc.atomwise_energy(hsd64, h, b, 1, z=zz)
+            y = orc.atomwise_contributions(hsd64, h, zz)
+            out = {"h": h.detach(), "X": X.detach(), "energy": e.detach(), "energy_mass": y.detach().abs().sum()}
+            if forces:
+                (g,) = torch.autograd.grad(e.sum(), p64, retain_graph=upstream is not None)
+                out["forces"] = -g
+            if upstream is not None:
+                wh, wX = (u.detach().cpu()[rows].double() for u in upstream)
+                (out["pos_grad_h"],) = torch.autograd.grad((h * wh).sum(), p64, retain_graph=True)
+                (out["pos_grad_X"],) = torch.autograd.grad((X * wX).sum(), p64)
+    finally:
+        torch.set_num_threads(old_threads)
+    _ORACLE_CACHE[key] = out
+    return out

@@ -961,6 +961,39 @@ def test_in_flight_inputs_may_be_freed_right_after_the_call():
 
 
 @pytest.mark.gpu
+def test_in_flight_after_repeated_weight_updates():
+    """InFlight fences the first call of a kind after a weight update (the call that builds the new pack's lazily
+    cached operands) against the other lanes.  The cold-call key is a generation number bumped with every new pack -- an id()
+    of a freed pack can come back for a later pack and would have skipped the fence.  Four in-place updates, each followed by
+    six calls that cycle through the three lanes: every result is the bits of a plain EnergyForces on the same weights."""
+    from tests.test_hip_forces import _head_from_case
+    from gotennet_amd.graph import distance
+    from gotennet_amd.pipeline import EnergyForces, InFlight
+    cfg, sd, head_sd, t = load_case("l2_sep_f32")
+    net, head = _mirror(cfg, sd), _head_from_case(cfg, head_sd)
+    z, batch = t["z"].cuda(), t["batch"].cuda()
+    g = torch.Generator().manual_seed(7)
+    cases = [distance((t["pos"] + 0.05 * torch.randn(t["pos"].shape, generator=g)).cuda(), batch, cfg["cutoff"], 32)
+             for _ in range(3)]
+    fl = InFlight(net, head, lanes=3, check_edges=False, cache_topology=False)
+    plain = EnergyForces(net, head, check_edges=False, cache_topology=False)
+    weights = [net.gata_list[0].W_q.weight, net.eqff_list[-1].gamma_m[0].weight, net.gata_list[-1].W_re.weight,
+               net.node_init.A_nbr.weight]
+    for u in range(len(weights) + 1):
+        if u:
+            with torch.no_grad():
+                weights[u - 1].mul_(1.0 + 1e-3 * u)          # in place: same storage, new version -> a new pack
+        out = [fl(z, *cases[k % 3], batch, cfg["n_mol"]) for k in range(6)]
+        fl.wait()
+        keep = [(e.clone(), f.clone()) for e, f in out]
+        ref = [plain(z, *c, batch, cfg["n_mol"]) for c in cases]
+        torch.cuda.synchronize()
+        for k, (e, f) in enumerate(keep):
+            assert torch.equal(e, ref[k % 3][0]) and torch.equal(f, ref[k % 3][1]), (u, k)
+        assert len(fl._seen) == 1                            # the cold-call keys of earlier packs are dropped
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("agg,atomref", [("sum", True), ("mean", False), (None, False)])
 def test_atomwise_n_out_3_matches_oracle(agg, atomref):
     """VERDICT r5 breadth: ``Atomwise(n_out > 1)`` (reference outputs.py:241, 323-376).  Energies [n_mol, 3], forces of the SUM of the
