@@ -772,9 +772,21 @@ def _edge_update_composed_backward(cfg: Config, lw: LayerWeights, lt, gt, gt_a, 
 
 
 def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, tape: Tape,
-             gh: torch.Tensor, gX: Optional[torch.Tensor]):
+             gh: torch.Tensor, gX: Optional[torch.Tensor], trace: Optional[list] = None):
     """Input-gradients of ``forward``: given dL/dh [N,F] and dL/dX [N,D,F] (or None = 0)
-    returns (g_edge_vec [E,3], g_edge_diff [E]) in the CSR edge order of ``g``."""
+    returns (g_edge_vec [E,3], g_edge_diff [E]) in the CSR edge order of ``g``.
+
+    ``trace`` (tests only) collects clones of the adjoints at every stage boundary, in the model's real channel layout, as
+    dicts with a ``stage`` key: "layer" (dL/d of layer ``layer``'s output h, X, t; zeros where no gradient flows),
+    "message" (dL/d of its message stage's output h, X: what EQFF and HTR read), "norm" (dL/d of its normalised inputs,
+    with layernorm / steerable_norm only) and "init" (dL/dh0, dL/dt0, dL/dphi, dL/dX of the initial zero X, dL/d edge_vec,
+    dL/d edge_diff).  An adjoint the backward never computes (dL/dX_in of a zero-X_in layer) is recorded as None."""
+    snap = None
+    if trace is not None:
+        def snap(stage, li, **ts):
+            sel = lambda k, v: (v.clone() if pw.emb_idx is None or k in ("phi", "vec", "diff") else
+                                v.index_select(v.dim() - 1, pw.emb_idx))
+            trace.append(dict(stage=stage, layer=li, **{k: None if v is None else sel(k, v) for k, v in ts.items()}))
     F_, R, H, D, M, lmax = cfg.F, cfg.R, cfg.H, cfg.D, cfg.M, cfg.lmax
     Fe = cfg.Fe
     N, E = g.N, g.E
@@ -830,6 +842,9 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
         lw, lt = pw.layers[li], tape.layers[li]
         last = lw.Wt is None
         first = zero_X_in(cfg, li)
+        if snap is not None:
+            snap("layer", li, h=gh, X=gX if gX is not None else torch.zeros((N, D, F_), **f32),
+                 t=gt if gt is not None else torch.zeros((E, F_), **f32))
         # ---- EQFF backward (one kernel where covered; else its first half here); HTR backward kernels (independent of it)
         m1 = None
         if eq_fused:
@@ -896,6 +911,8 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
                 off += cnt
                 if joint:
                     break
+        if snap is not None:
+            snap("message", li, h=gh1, X=gX1)
         # ---- message backward
         if first and G > 1:                        # one launch instead of G degree groups: one g_cut slice is written
             g_cut_parts[G * li + 1:G * li + G].zero_()       # (never together with wide slots: zero_X_in excludes them)
@@ -929,6 +946,8 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
         if gX2 is gX_caller:
             gX2 = new(N, D, F_)
         gt, gt_b = gt_b, (gt if gt is not None else new(E, F_))
+        if snap is not None and (cfg.layernorm or cfg.steerable_norm):
+            snap("norm", li, h=gh, X=None if first else gX)
         # ---- optional input norms (gotennet.py:397-398): back to the un-normalised h / X
         if cfg.layernorm:
             if pw.emb_idx is None:
@@ -967,6 +986,8 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
     call("gn_edge_geometry_backward", ptr(g.edge_vec), ptr(g.edge_diff), ptr(g.src), ptr(g.dst), E, lmax, R,
          cfg.basis, ptr(pw.rb0), ptr(pw.rb1), float(cfg.cutoff), ptr(g_rl_parts), n_rl, ptr(g_cut_parts), n_cut,
          ptr(g_phi), ptr(g_vec), ptr(g_diff), _stream())
+    if snap is not None:
+        snap("init", -1, h=gh, t=gt, phi=g_phi, X=None if zero_X_in(cfg, 0) else gX, vec=g_vec, diff=g_diff)
     return g_vec, g_diff
 
 
