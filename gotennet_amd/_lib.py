@@ -14,10 +14,11 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GN_LIB_PATH") or os.path.join(_PKG, "libgotennet_hip.so")
 
 GN_ERR_BAD_ARG = 10001
-ABI_VERSION = 8
+ABI_VERSION = 9
 LMAX_SLICED = 0x100      # GN_LMAX_SLICED: OR-ed into the lmax argument of the message / HTR entry points
 LMAX_MEAN, LMAX_MAX = 0x200, 0x400      # GN_LMAX_MEAN / GN_LMAX_MAX: the reference's aggr = "mean" / "max" (message entries)
 
+ACT_NONE = 11            # GN_ACT_NONE
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_long
 
 # symbol -> argtypes (mirrors include/gotennet_hip.h one for one)
@@ -29,6 +30,13 @@ class GemmDesc(C.Structure):
                 ("res", _P), ("gate", _P), ("gate_mode", _I), ("pre_out", _P),
                 ("pro_mode", _I), ("pro_lo", _I), ("pro_hi", _I), ("a_pre", _P), ("ldp", _I),
                 ("a_gate", _P), ("ldg", _I), ("A2", _P), ("A3", _P), ("a_seg", _I), ("act_kind", _I)]
+
+
+class WgradDesc(C.Structure):
+    """gn_wgrad_desc of include/gotennet_hip.h (one problem of gn_weight_grad_group)."""
+    _fields_ = [("dY", _P), ("ldy", _I), ("y_off", _I), ("A", _P), ("lda", _I), ("a_off", _I),
+                ("dW", _P), ("ldw", _I), ("db", _P), ("rows", _I), ("nout", _I), ("K", _I),
+                ("row_cnt", _I), ("row_gstride", _I), ("row_goff", _I)]
 
 
 SIGNATURES = {
@@ -89,7 +97,14 @@ SIGNATURES = {
     "gn_ese_reduce": [_P, _P, _P, _P, _I, _P, _I, _P, _P],
     "gn_radius_count": [_P, _P, _I, _F, _I, _P, _P],
     "gn_radius_fill": [_P, _P, _I, _F, _I, _P, C.c_int64, _P, _P, _P, _P],
+    "gn_weight_grad_workspace": [_P, _I],
+    "gn_weight_grad_group": [_P, _I, _P, _L, _P],
+    "gn_embedding_grad": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "gn_layernorm_param_grad_workspace": [_I, _I],
+    "gn_layernorm_param_grad": [_P, _P, _P, _F, _P, _I, _I, _I, _P, _P, _P, _P],
 }
+
+_LONG_RESULT = ("gn_split_bf16x3_size", "gn_split_f16x2_size", "gn_weight_grad_workspace", "gn_layernorm_param_grad_workspace")
 
 _lib = None
 
@@ -111,7 +126,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes
-        fn.restype = C.c_long if name in ("gn_split_bf16x3_size", "gn_split_f16x2_size") else C.c_int
+        fn.restype = C.c_long if name in _LONG_RESULT else C.c_int
     if lib.gn_abi_version(None) != ABI_VERSION:
         raise GotenNetHipError("libgotennet_hip.so ABI version mismatch; rebuild")
     _lib = lib

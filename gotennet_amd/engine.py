@@ -15,6 +15,7 @@ producing GEMM's epilogue.  Independent projections are issued as grouped launch
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
@@ -398,11 +399,15 @@ class LayerTape:
     w_raw: torch.Tensor = None; h_raw: torch.Tensor = None; X_raw: torch.Tensor = None
     upd: dict = None                               # intermediates of the composed edge update
     Xp: torch.Tensor = None; ctx: torch.Tensor = None; pre_g1: torch.Tensor = None; mm: torch.Tensor = None
+    # parameter gradients only: X after the message stage (EQFF then updates X in place), the activated node projections
+    # (columns 2F:4F: the inputs of gamma_s.1 / gamma_v.1) and act(pre_g1) (the input of gamma_m.1)
+    X_msg: torch.Tensor = None; nact: torch.Tensor = None; g1act: torch.Tensor = None
 
 
 @dataclass
 class Tape:
     feat: torch.Tensor = None; y_pre: torch.Tensor = None; h0: torch.Tensor = None
+    ctx0: torch.Tensor = None; y: torch.Tensor = None           # parameter gradients only: inputs of W_nrd_nru.{0,1}
     layers: List[LayerTape] = field(default_factory=list)
 
 
@@ -413,15 +418,38 @@ def check_backward_supported(cfg: Config) -> None:
                                   "attention head inside one wave (at most 256 channels per head)")
 
 
+def check_param_grads_supported(cfg: Config) -> None:
+    """Raise NotImplementedError -- BEFORE any launch -- for the configurations whose parameter gradients do not exist
+    (``parameter_grads``): composed edge updates, widths that are not a power of two, and whatever has no force path."""
+    if cfg.composed_update:
+        raise NotImplementedError("parameter_grads: composed edge updates (edge_updates with 'mlp' / 'mlpa' / 'linw' / "
+                                  "'linwa'; evec_dim != n_atom_basis needs one) have no parameter-gradient path")
+    if cfg.F_model or cfg.F & (cfg.F - 1):
+        raise NotImplementedError(f"parameter_grads: n_atom_basis={cfg.F_model or cfg.F} is not a power of two (the model "
+                                  "runs embedded in a wider one); parameter gradients need a power-of-two width")
+    check_backward_supported(cfg)
+
+
+def param_grad_config(cfg: Config) -> Config:
+    """The configuration a parameter-gradient forward / backward runs: the un-fused EQFF chain (the fused kernels never
+    materialise g_m, dL/d pre_g1 or act(pre_g1))."""
+    return dataclasses.replace(cfg, fuse_eqff=False)
+
+
 def _forward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, save: bool = False,
-            trace: Optional[list] = None):
-    """-> (h [N,F], X [N,D,F], tape or None).  ``save`` keeps what ``backward`` needs;
+            trace: Optional[list] = None, pgrads: bool = False):
+    """-> (h [N,F], X [N,D,F], tape or None).  ``save`` keeps what ``backward`` needs; ``pgrads`` (with ``save``, and a
+    ``param_grad_config``) also keeps the inputs of every projection for the parameter gradients;
     ``trace`` (tests only) collects per-layer clones of (h, X, t)."""
     F_, R, H, D, M, lmax = cfg.F, cfg.R, cfg.H, cfg.D, cfg.M, cfg.lmax
     Fe = cfg.Fe
     N, E = g.N, g.E
     if save:
         check_backward_supported(cfg)               # before any launch: a saving forward is only run for a backward
+    if pgrads:
+        check_param_grads_supported(cfg)
+        if not save or cfg.fuse_eqff is not False:
+            raise ValueError("internal: a parameter-gradient forward saves its tape and runs the un-fused EQFF chain")
     proj = _Proj(cfg)
     gemm, gemm_group = proj.gemm, proj.group
     dev = z32.device
@@ -446,6 +474,8 @@ def _forward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, s
     call("gn_edge_init", ptr(h), ptr(g.rowptr), ptr(g.src), feat.data_ptr() + 4 * F_, 2 * F_, N, F_, ptr(t), _stream())
     if save:
         tape.feat, tape.y_pre, tape.h0 = feat, y_pre, h
+    if pgrads:
+        tape.ctx0, tape.y = ctx0, y
 
     # gotennet.py:992: X starts as the zero tensor.  Where the first interaction runs the zero-X_in kernels nothing ever reads
     # it (message stage and message backward get a null X_in): no fill launch
@@ -482,6 +512,9 @@ def _forward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, s
                 lt.w_raw = new(E, Fe) if (cfg.htr_mode >> 2) else None
             lt.nproj, lt.xs, lt.vs, lt.eproj, lt.attn = nproj, xs, vs, eproj, attn
             lt.Xp, lt.ctx, lt.pre_g1, lt.mm = Xp, ctx, pre_g1, mm
+            if pgrads:                             # activated copies: one per layer instead of the shared scratch
+                nact, g1act = new(N, 4 * F_), new(N, F_)
+                lt.nact, lt.g1act = nact, g1act
         # ---- GATA projections (gotennet.py:400-407).  The atom-sized node projection rides in the edge projection's
         # launch (its 168 tiles fill the tail of the 5100-tile grid).  SiLU of the two hidden blocks is applied ONCE by
         # the epilogue (a SiLU prologue in the two products below would redo it for each of their 4M column tiles); the
@@ -500,6 +533,8 @@ def _forward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, s
         message_stage(cfg, g, nact, xs, vs, eproj, attn, h, None if first else X, h2, X2)
         h, h2 = h2, h
         X, X2 = X2, X
+        if pgrads:
+            lt.X_msg = X.clone()
         # every product of the updated X (X W_vu^T for EQFF; EQ and the per-degree EK_l for HTR) in one launch
         xprods = [dict(A=X, lda=F_, W=lw.Wvu, C=Xp, ldc=F_, rows=N * D, nout=F_, K=F_)]
         if not last:
@@ -771,10 +806,61 @@ def _edge_update_composed_backward(cfg: Config, lw: LayerWeights, lt, gt, gt_a, 
     return gq
 
 
+def weight_grad_group(problems):
+    """Several independent weight gradients dW = dY^T A (+ db = sum_r dY) as one launch (gn_weight_grad_group).  A
+    problem is a dict: dY, ldy, A, lda, dW (its rows [w_row, w_row + nout) are written), rows, nout, K; optional y_off,
+    a_off (column offsets), db (with b_row), rowmap (cnt, gstride, goff)."""
+    problems = [q for q in problems if q is not None]
+    if not problems:
+        return
+    arr = (_lib.WgradDesc * len(problems))()
+    for d, q in zip(arr, problems):
+        g = q.get
+        dW = q["dW"]
+        d.dY, d.ldy, d.y_off = q["dY"].data_ptr(), q["ldy"], g("y_off", 0)
+        d.A, d.lda, d.a_off = q["A"].data_ptr(), q["lda"], g("a_off", 0)
+        d.dW, d.ldw = dW.data_ptr() + 4 * g("w_row", 0) * dW.shape[-1], dW.shape[-1]
+        db = g("db")
+        d.db = (db.data_ptr() + 4 * g("b_row", 0)) if db is not None else None
+        d.rows, d.nout, d.K = q["rows"], q["nout"], q["K"]
+        d.row_cnt, d.row_gstride, d.row_goff = g("rowmap", (1, 1, 0))
+    lib = _lib.load()
+    work = torch.empty(max(1, lib.gn_weight_grad_workspace(arr, len(problems))), dtype=torch.float32,
+                       device=problems[0]["dW"].device)
+    call("gn_weight_grad_group", arr, len(problems), ptr(work), work.numel(), _stream())
+
+
+def layernorm_param_grad(x, gamma, beta, g_out, act: int, dgamma, dbeta):
+    """dgamma, dbeta of a LayerNorm over the last axis of x [N, C] (eps 1e-5) followed by the activation ``act``
+    (GN_ACT_NONE: a bare nn.LayerNorm); g_out is the gradient at the activation's output."""
+    N, C = x.shape
+    work = torch.empty(max(1, _lib.load().gn_layernorm_param_grad_workspace(N, C)), dtype=torch.float32, device=x.device)
+    call("gn_layernorm_param_grad", ptr(x), ptr(gamma), ptr(beta), 1e-5, ptr(g_out), N, C, act, ptr(work), ptr(dgamma),
+         ptr(dbeta), _stream())
+
+
+def empty_grads(pw: PackedWeights) -> PackedWeights:
+    """Gradient storage in the layout of the pack (every trainable operand; buffers stay None).  The parameter-gradient
+    backward writes every element."""
+    e = lambda t: None if t is None else torch.empty_like(t)
+    out = PackedWeights(A_na=e(pw.A_na), A_nbr=e(pw.A_nbr), Winit=e(pw.Winit), binit=e(pw.binit), Wa=e(pw.Wa), ba=e(pw.ba),
+                        ln_w=e(pw.ln_w), ln_b=e(pw.ln_b), Wb=e(pw.Wb), bb=e(pw.bb), rb0=None, rb1=None)
+    for lw in pw.layers:
+        out.layers.append(LayerWeights(
+            Wn1=e(lw.Wn1), bn1=e(lw.bn1), Ws2=e(lw.Ws2), bs2=e(lw.bs2), Wv2=e(lw.Wv2), bv2=e(lw.bv2), We=e(lw.We), be=e(lw.be),
+            Wvu=e(lw.Wvu), Wm0=e(lw.Wm0), bm0=e(lw.bm0), Wm1=e(lw.Wm1), bm1=e(lw.bm1), Wt=e(lw.Wt), bt=e(lw.bt),
+            Wvq=e(lw.Wvq), Wvk=[e(w) for w in lw.Wvk], ln_w=e(lw.ln_w), ln_b=e(lw.ln_b)))
+    return out
+
+
 def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, tape: Tape,
-             gh: torch.Tensor, gX: Optional[torch.Tensor], trace: Optional[list] = None):
+             gh: torch.Tensor, gX: Optional[torch.Tensor], trace: Optional[list] = None,
+             pgrads: Optional[PackedWeights] = None, geometry: bool = True):
     """Input-gradients of ``forward``: given dL/dh [N,F] and dL/dX [N,D,F] (or None = 0)
     returns (g_edge_vec [E,3], g_edge_diff [E]) in the CSR edge order of ``g``.
+
+    ``pgrads`` (storage from ``empty_grads``; the tape of a ``pgrads`` forward): also writes dL/d of every packed weight
+    into it.  ``geometry=False`` skips the edge-geometry backward (no position gradient wanted) and returns (None, None).
 
     ``trace`` (tests only) collects clones of the adjoints at every stage boundary, in the model's real channel layout, as
     dicts with a ``stage`` key: "layer" (dL/d of layer ``layer``'s output h, X, t; zeros where no gradient flows),
@@ -795,6 +881,10 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
     f32 = dict(dtype=torch.float32, device=z32.device)
     new = lambda *shape: torch.empty(shape, **f32)
     check_backward_supported(cfg)
+    if pgrads is not None:
+        check_param_grads_supported(cfg)
+        if cfg.fuse_eqff is not False or tape.ctx0 is None:
+            raise ValueError("internal: parameter gradients need the tape of a parameter-gradient forward")
     colptr, perm = g.csc()
     lde = (1 + M) * F_
     eq_fused, eq_arith = eqff_fused_ok(cfg, N), (1 if proj.mode == "split" else 2)
@@ -878,6 +968,24 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
         if not eq_fused:
             gemm(g_g1, F_, _T(lw, "Wm0"), None, g_ctx, 2 * F_, N, 2 * F_, F_)
             call("gn_eqff_backward_b", ptr(g_ctx), ptr(lt.ctx), ptr(lt.Xp), ptr(gh), N, F_, D, ptr(gXp), ptr(gh1), _stream())
+        if pgrads is not None:                     # before the next layer's backward reuses gm, g_g1, gXp, g_pre_t, gEQ, gEK
+            gw = pgrads.layers[li]
+            probs = [dict(dY=gm, ldy=2 * F_, A=lt.g1act, lda=F_, dW=gw.Wm1, db=gw.bm1, rows=N, nout=2 * F_, K=F_),
+                     dict(dY=g_g1, ldy=F_, A=lt.ctx, lda=2 * F_, dW=gw.Wm0, db=gw.bm0, rows=N, nout=F_, K=2 * F_),
+                     dict(dY=gXp, ldy=F_, A=lt.X_msg, lda=F_, dW=gw.Wvu, rows=N * D, nout=F_, K=F_)]
+            if not last:
+                probs += [dict(dY=g_pre_t, ldy=F_, A=lt.t_in, lda=F_, dW=gw.Wt, db=gw.bt, rows=E, nout=F_, K=F_),
+                          dict(dY=gEQ, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvq, rows=N * D, nout=Fe, K=F_)]
+                if cfg.htr_mode & 1:
+                    probs.append(dict(dY=gEK, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvk[0], rows=N * D, nout=Fe, K=F_))
+                else:
+                    off = 0
+                    for l in range(1, lmax + 1):
+                        cnt = 2 * l + 1
+                        probs.append(dict(dY=gEK, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvk[l - 1], rows=N * cnt, nout=Fe, K=F_,
+                                          rowmap=(cnt, D, off)))
+                        off += cnt
+            weight_grad_group(probs)
         # ---- gX1 = gX + gXp W_vu (+ gEQ W_vq + gEK_l W_vk_l)
         joint = bool(cfg.htr_mode & 1)
         if last:
@@ -939,6 +1047,21 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
                     # too and halves the K of the product that has to wait for the two riders above (33 -> 20 us)
                     dict(A=g_nproj, lda=4 * F_, W=_Tqk(lw), C=gh_qk, ldc=F_, rows=N, nout=F_, K=2 * F_, res=gh1)])
         gemm(g_nproj, 4 * F_, _Tsv(lw), None, gh2, F_, N, F_, 2 * F_, res=gh_qk, a_off=2 * F_)
+        if pgrads is not None:                     # g_eproj, g_nproj, g_x, g_v are final; the next layer reuses them
+            gw = pgrads.layers[li]
+            ne = ke if first else lde               # layer 0 with zero X_in: the tensor-gate rows get exactly zero
+            nv = _value_first(cfg, lw) if first else M * F_
+            weight_grad_group([
+                dict(dY=g_eproj, ldy=lde, A=lt.t_in, lda=F_, dW=gw.We, db=gw.be, rows=E, nout=ne, K=F_),
+                dict(dY=g_nproj, ldy=4 * F_, A=lt.h_in, lda=F_, dW=gw.Wn1, db=gw.bn1, rows=N, nout=4 * F_, K=F_),
+                dict(dY=g_x, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=2 * F_, dW=gw.Ws2, db=gw.bs2, rows=N, nout=nv, K=F_),
+                dict(dY=g_v, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=3 * F_, dW=gw.Wv2, db=gw.bv2, rows=N, nout=nv, K=F_)])
+            if ne < lde:
+                gw.We[ne:].zero_()
+                gw.be[ne:].zero_()
+            if nv < M * F_:
+                for t_ in (gw.Ws2, gw.bs2, gw.Wv2, gw.bv2):
+                    t_[nv:].zero_()
         gh, gh2 = gh2, gh
         gX, gX2 = gX2, gX
         if gh2 is gh_caller:
@@ -950,6 +1073,9 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
             snap("norm", li, h=gh, X=None if first else gX)
         # ---- optional input norms (gotennet.py:397-398): back to the un-normalised h / X
         if cfg.layernorm:
+            if pgrads is not None:                 # gh: dL/d of the normalised h
+                layernorm_param_grad(lt.h_raw, lw.ln_w, lw.ln_b, gh, _lib.ACT_NONE, pgrads.layers[li].ln_w,
+                                     pgrads.layers[li].ln_b)
             if pw.emb_idx is None:
                 call("gn_layernorm_backward", ptr(lt.h_raw), ptr(lw.ln_w), 1e-5, ptr(gh), N, F_, ptr(gh2), _stream())
             else:                                  # statistics over the real channels: compact -> kernel -> padded layout
@@ -980,6 +1106,22 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
     gemm(gy1, Fc, _T(pw, "Wa"), None, g_ctx, 2 * F_, N, 2 * F_, Fc)
     call("gn_node_init_backward", ptr(g_ctx), ptr(z32), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(pw.A_nbr),
          ptr(g.rowptr), ptr(g.src), N, F_, ptr(g_feat), cut_slice(Wm * G * L), _stream())
+    if pgrads is not None:
+        layernorm_param_grad(tape.y_pre, pw.ln_w, pw.ln_b, gy, cfg.act, pgrads.ln_w, pgrads.ln_b)
+        weight_grad_group([dict(dY=gh, ldy=F_, A=tape.y, lda=Fc, dW=pgrads.Wb, db=pgrads.bb, rows=N, nout=F_, K=Fc),
+                           dict(dY=gy1, ldy=Fc, A=tape.ctx0, lda=2 * F_, dW=pgrads.Wa, db=pgrads.ba, rows=N, nout=Fc, K=2 * F_),
+                           dict(dY=g_feat, ldy=2 * F_, A=g.phi, lda=R, dW=pgrads.Winit, db=pgrads.binit, rows=E, nout=2 * F_,
+                                K=R)])
+        # species order of the atoms (integer plumbing): a stable argsort of z and the first sorted position of each species
+        n_sp = pw.A_na.shape[0]
+        zs, order = torch.sort(z32.long(), stable=True)
+        sp_ptr = torch.searchsorted(zs, torch.arange(n_sp + 1, device=zs.device)).to(torch.int32)
+        order = order.to(torch.int32)
+        per_src = new(N, F_)                       # per-source sums of the A_nbr gradient (named: alive until the launch)
+        call("gn_embedding_grad", ptr(g_ctx), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(g.dst), ptr(colptr), ptr(perm),
+             ptr(order), ptr(sp_ptr), n_sp, N, F_, ptr(per_src), ptr(pgrads.A_na), ptr(pgrads.A_nbr), _stream())
+        if not geometry:
+            return None, None
     g_phi = new(E, R)
     gemm(g_feat, 2 * F_, _T(pw, "Winit"), None, g_phi, R, E, R, 2 * F_)
     g_vec, g_diff = new(E, 3), new(E)

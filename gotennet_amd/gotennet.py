@@ -65,6 +65,142 @@ class _RepresentationPosFn(torch.autograd.Function):
         return engine.pos_gradient(g, g_vec, g_diff, sign=1.0), None, None, None
 
 
+def refuse_second_order(what: str) -> None:
+    """A backward that runs with create_graph=True (a loss on forces from autograd.grad(E, pos, create_graph=True)) would
+    need the derivative of this backward: refuse it rather than return parameter gradients without the force term."""
+    if torch.is_grad_enabled():
+        raise NotImplementedError(f"{what}: force-loss training needs a second-order backward (create_graph=True), which "
+                                  "the parameter-gradient path does not have; train on energies and / or (h, X) only")
+
+
+class positions_only:
+    """``with positions_only(y): torch.autograd.grad(y, [pos])``: the parameter-gradient Functions of the graph that ends in
+    ``y`` compute the input-gradient alone during this call (no weight-gradient work; their parameter gradients come back
+    as None, which autograd.grad discards when only positions are asked for).  Used by ``Atomwise`` for the forces it
+    logs with ``derivative``; a later ``loss.backward()`` on the same graph computes the parameter gradients.  The flag
+    lives on the graph's own nodes, so other graphs (and other threads) are unaffected."""
+
+    def __init__(self, y: Tensor):
+        self.nodes = []
+        stack, seen, alive = [y.grad_fn], set(), []    # (alive: visited wrappers keep their ids unique)
+        while stack and len(seen) < 100000:
+            n = stack.pop()
+            if n is None or id(n) in seen:
+                continue
+            seen.add(id(n))
+            alive.append(n)
+            if getattr(n, "gn_param_fn", False):
+                self.nodes.append(n)
+            stack.extend(f for f, _ in n.next_functions)
+
+    def __enter__(self):
+        for n in self.nodes:
+            n.gn_positions_only = True
+        return self
+
+    def __exit__(self, *exc):
+        for n in self.nodes:
+            n.gn_positions_only = False
+        return False
+
+
+def _param_forward(ctx, net, z32, g, params):
+    ctx.gn_param_fn, ctx.gn_positions_only = True, False
+    cfg, pw = ctx.cfg, ctx.pw
+    h, X, tape = engine.forward(cfg, pw, z32, g, save=True, pgrads=True)
+    ctx.state = (cfg, pw, z32, g, tape, net, params)
+    return h, X
+
+
+def _param_backward(ctx, gh, gX, geometry: bool, n_lead: int):
+    """-> (g_vec, g_diff, parameter gradients in the order of the Function's trailing inputs, None where not wanted)."""
+    refuse_second_order("GotenNet.parameter_grads")
+    cfg, pw, z32, g, tape, net, params = ctx.state
+    if ctx.gn_positions_only:                     # positions_only(): the input-gradient backward alone
+        g_vec, g_diff = engine.backward(cfg, pw, z32, g, tape, gh, gX)
+        return g_vec, g_diff, [None] * len(params)
+    grads = engine.empty_grads(pw)
+    g_vec, g_diff = engine.backward(cfg, pw, z32, g, tape, gh, gX, pgrads=grads, geometry=geometry)
+    by_id = unpack_param_grads(net, grads, by_id=True)
+    pg = [by_id[id(p)] if ctx.needs_input_grad[n_lead + i] else None for i, p in enumerate(params)]
+    return g_vec, g_diff, pg
+
+
+class _RepresentationParamFn(torch.autograd.Function):
+    """(edge_diff, edge_vec, *parameters) -> (h, X) with parameter gradients (``GotenNet.parameter_grads``)."""
+
+    @staticmethod
+    def forward(ctx, edge_diff, edge_vec, net, z32, edge_index, cfg, pw, *params):
+        ctx.cfg, ctx.pw = cfg, pw
+        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff.detach(), edge_vec.detach())
+        return _param_forward(ctx, net, z32, g, params)
+
+    @staticmethod
+    def backward(ctx, gh, gX):
+        geometry = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        g_vec, g_diff, pg = _param_backward(ctx, gh, gX, geometry, 7)
+        return (g_diff, g_vec, None, None, None, None, None, *pg)
+
+
+class _RepresentationPosParamFn(torch.autograd.Function):
+    """(pos, *parameters) -> (h, X) including the radius graph, with parameter gradients."""
+
+    @staticmethod
+    def forward(ctx, pos, net, z32, batch, cfg, pw, *params):
+        from .graph import distance
+        ctx.cfg, ctx.pw = cfg, pw
+        edge_index, edge_diff, edge_vec = distance(pos.detach(), batch, net.cutoff, net.max_num_neighbors)
+        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff, edge_vec)
+        return _param_forward(ctx, net, z32, g, params)
+
+    @staticmethod
+    def backward(ctx, gh, gX):
+        g_vec, g_diff, pg = _param_backward(ctx, gh, gX, ctx.needs_input_grad[0], 6)
+        g_pos = engine.pos_gradient(ctx.state[3], g_vec, g_diff, sign=1.0) if ctx.needs_input_grad[0] else None
+        return (g_pos, None, None, None, None, None, *pg)
+
+
+def unpack_param_grads(net, packed: engine.PackedWeights, by_id: bool = False):
+    """The exact inverse of the concatenations of ``packed_weights()``: -> {parameter name: tensor in the parameter's own
+    shape} in ``named_parameters()`` order (or {id(parameter): tensor} with ``by_id``).  Applied to a gradient pack
+    (engine.empty_grads, filled by the backward) it gives every parameter's gradient; applied to ``net.packed_weights()``
+    the parameters themselves."""
+    F_ = net.n_atom_basis
+    ni, ei = net.node_init, net.edge_init
+    mlp = ni.W_nrd_nru.dense_layers
+    ndp = ni.W_ndp.dense_layers[0]
+    pairs = [(net.A_na.weight, packed.A_na), (ni.A_nbr.weight, packed.A_nbr),
+             (ndp.weight, packed.Winit[:F_]), (ei.W_erp.weight, packed.Winit[F_:]),
+             (ndp.bias, packed.binit[:F_]), (ei.W_erp.bias, packed.binit[F_:]),
+             (mlp[0].weight, packed.Wa), (mlp[0].bias, packed.ba), (mlp[0].norm.weight, packed.ln_w),
+             (mlp[0].norm.bias, packed.ln_b), (mlp[1].weight, packed.Wb), (mlp[1].bias, packed.bb)]
+    for gata, eq, lw in zip(net.gata_list, net.eqff_list, packed.layers):
+        blocks = (gata.W_q, gata.W_k, gata.gamma_s[0], gata.gamma_v[0])       # W_n1 = [W_q; W_k; gamma_s.0; gamma_v.0]
+        for i, m in enumerate(blocks):
+            pairs += [(m.weight, lw.Wn1[i * F_:(i + 1) * F_]), (m.bias, lw.bn1[i * F_:(i + 1) * F_])]
+        pairs += [(gata.gamma_s[1].weight, lw.Ws2), (gata.gamma_s[1].bias, lw.bs2),
+                  (gata.gamma_v[1].weight, lw.Wv2), (gata.gamma_v[1].bias, lw.bv2),
+                  (gata.W_re.weight, lw.We[:F_]), (gata.W_re.bias, lw.be[:F_]),   # W_e = [W_re; W_rs]
+                  (gata.W_rs.weight, lw.We[F_:]), (gata.W_rs.bias, lw.be[F_:])]
+        if not gata.last_layer and gata.edge_updates:
+            dl = gata.gamma_t.dense_layers[-1]
+            pairs += [(dl.weight, lw.Wt), (dl.bias, lw.bt), (gata.W_vq.weight, lw.Wvq)]
+            wk = list(gata.W_vk) if gata.sep_htr else [gata.W_vk]
+            pairs += [(m.weight, w) for m, w in zip(wk, lw.Wvk)]
+        if gata.layernorm_:
+            pairs += [(gata.layernorm.weight, lw.ln_w), (gata.layernorm.bias, lw.ln_b)]
+        pairs += [(eq.W_vu.weight, lw.Wvu), (eq.gamma_m[0].weight, lw.Wm0), (eq.gamma_m[0].bias, lw.bm0),
+                  (eq.gamma_m[1].weight, lw.Wm1), (eq.gamma_m[1].bias, lw.bm1)]
+    got = {id(p): v.reshape(p.shape) for p, v in pairs}
+    named = list(net.named_parameters())
+    missing = [n for n, p in named if id(p) not in got]
+    if missing:
+        raise NotImplementedError(f"parameter_grads: no packed operand for {missing}")
+    if by_id:
+        return got
+    return {n: got[id(p)] for n, p in named}
+
+
 def _pack_gata(gata) -> engine.LayerWeights:
     """GEMM operands of one GATA layer: projections that share an input are concatenated into one weight."""
     c = lambda *ts: torch.cat([t.detach() for t in ts], dim=0).contiguous()
@@ -424,6 +560,10 @@ class GotenNet(nn.Module):
         #: engine.EQFF_FUSED_MAX_ATOMS atoms (a one-molecule step is launch-bound: 2.31 -> 1.91 ms; 32 molecules -2 %), off
         #: above (the 128-molecule batch: 7.735 vs 7.698 ms); True / False force it
         self.fuse_eqff = None
+        #: True: a forward with grad mode on and some parameter requiring grad runs through an autograd Function that
+        #: takes the parameters as inputs, and the backward writes d loss / d parameter for every parameter that requires
+        #: grad (first order: a loss on energies and / or (h, X); engine.check_param_grads_supported lists what is refused)
+        self.parameter_grads = False
         self._warned_inference_only = False
 
     # ------------------------------------------------------------------ parameters
@@ -579,6 +719,18 @@ class GotenNet(nn.Module):
         if self.training and self.attn_dropout > 0:
             raise NotImplementedError("attention dropout (training mode) is not on the accelerated path; call .eval()")
 
+    def _param_path(self) -> Optional[list]:
+        """The parameters, when this call trains them (``parameter_grads``, grad mode on, one of them requires grad)."""
+        if not (self.parameter_grads and torch.is_grad_enabled()):
+            return None
+        params = list(self.parameters())
+        return params if any(p.requires_grad for p in params) else None
+
+    def _param_config(self):
+        cfg = self.config()
+        engine.check_param_grads_supported(cfg)          # before any launch
+        return engine.param_grad_config(cfg), self.packed_weights()
+
     def _warn_if_training(self):
         """The hand-written backward produces INPUT gradients only (forces).  In a training loop ``loss.backward()``
         would succeed and leave every ``param.grad`` None -- optimizers skip those silently -- so say it once."""
@@ -596,6 +748,9 @@ class GotenNet(nn.Module):
         """``_sorted`` (internal): this CALL's edge list is target-major (the wrapper's own radius graph); None = the
         module's ``assume_sorted_edges``.  A per-call argument, not module state: calls from several threads do not race."""
         self._check_inputs(atomic_numbers, edge_index, edge_diff, edge_vec)
+        params = self._param_path()
+        if params is not None:
+            engine.check_param_grads_supported(self.config())   # before any launch (the edge check below is one)
         cfg, pw = self.config(), self.packed_weights()
         N = atomic_numbers.shape[0]
         edge_index = edge_index.contiguous()
@@ -604,6 +759,9 @@ class GotenNet(nn.Module):
         if not (self.assume_sorted_edges if _sorted is None else _sorted):   # one host sync; skipped for sorted lists
             edge_index, edge_diff, edge_vec, _ = engine.sorted_edges(edge_index, edge_diff, edge_vec, N)
         z32 = atomic_numbers.to(torch.int32)
+        if params is not None:
+            cfg, pw = self._param_config()
+            return _RepresentationParamFn.apply(edge_diff, edge_vec, self, z32, edge_index, cfg, pw, *params)
         self._warn_if_training()
         if torch.is_grad_enabled() and (edge_vec.requires_grad or edge_diff.requires_grad):
             return _RepresentationFn.apply(edge_diff.contiguous(), edge_vec.contiguous(), self, z32, edge_index)
@@ -623,6 +781,12 @@ class GotenNetWrapper(GotenNet):
     def forward(self, inputs) -> Tuple[Tensor, Tensor]:
         from .graph import distance
         atomic_numbers, pos, batch = inputs.z, inputs.pos, inputs.batch
+        params = self._param_path()
+        if params is not None:                       # refused before any launch (the radius graph below is one)
+            self._check_inputs(atomic_numbers, torch.zeros((2, 0), dtype=torch.int64), pos.new_zeros(0), pos.new_zeros((0, 3)))
+            cfg, pw = self._param_config()
+            if pos.requires_grad:
+                return _RepresentationPosParamFn.apply(pos, self, atomic_numbers.to(torch.int32), batch, cfg, pw, *params)
         if torch.is_grad_enabled() and pos.requires_grad:
             self._warn_if_training()
             self._check_inputs(atomic_numbers, torch.zeros((2, 0), dtype=torch.int64), pos.new_zeros(0), pos.new_zeros((0, 3)))

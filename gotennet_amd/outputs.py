@@ -96,6 +96,9 @@ class Atomwise(nn.Module):
         stddev = torch.ones(1) if stddev is None else stddev
         self.standardize = ScaleShift(mean, stddev) if standardize else nn.Identity()
         self.atomref = nn.Embedding.from_pretrained(atomref.type(torch.float32)) if atomref is not None else None
+        #: True: with grad mode on and a parameter requiring grad, ``forward`` also returns d loss / d parameter for the
+        #: out_net layers (first order; a backward with create_graph=True is refused)
+        self.parameter_grads = False
 
     # ---- raw (non-autograd) pieces used by the fused pipeline -----------------------
     def invalidate_packed(self):
@@ -150,10 +153,11 @@ class Atomwise(nn.Module):
         return c["scale"], c["shift"]
 
     def energy_raw(self, h: torch.Tensor, z32: torch.Tensor, mol_ptr: torch.Tensor, n_mol: int, raw: bool = False,
-                   mode: Optional[str] = None):
+                   mode: Optional[str] = None, acts: Optional[list] = None):
         """-> (energy [n_mol,1] (sum or mean over the molecule's atoms), y [N] per-atom contributions, tape).
         ``tape`` (pre-activations of the hidden layers + the aggregation's per-atom weights) goes to ``grad_h_raw``.
-        ``raw``: y = the MLP output itself (no standardisation, no atomref) -- what ElectronicSpatialExtentV2 reads."""
+        ``raw``: y = the MLP output itself (no standardisation, no atomref) -- what ElectronicSpatialExtentV2 reads.
+        ``acts``: a list that receives the activated output of every hidden layer (the parameter gradients read them)."""
         layers, c = self._packed()
         N = h.shape[0]
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=h.device)
@@ -166,9 +170,15 @@ class Atomwise(nn.Module):
                 engine.gemm(x, d.in_features, c["w"][k], c["b"][k], xa, d.out_features, N, d.out_features, d.in_features,
                             act=(0, d.out_features), pre_out=pre, kind=self.act_kind, mode=mode)
                 x = xa
+            elif acts is not None:                   # ... and its activated copy for the last layer's weight gradient
+                xa = new(N, d.out_features)
+                engine.gemm(x, d.in_features, c["w"][k], c["b"][k], xa, d.out_features, N, d.out_features, d.in_features,
+                            act=(0, d.out_features), pre_out=pre, kind=self.act_kind, mode=mode)
             else:                                    # last hidden layer: gn_head_energy applies the activation itself
                 engine.gemm(x, d.in_features, c["w"][k], c["b"][k], pre, d.out_features, N, d.out_features, d.in_features,
                             kind=self.act_kind, mode=mode)
+            if acts is not None:
+                acts.append(xa)
             pres.append(pre)
         last_in = pres[-1] if pres else h.contiguous()
         act = self.act_kind if pres else 11          # GN_ACT_NONE: n_layers = 1, y = W h + b
@@ -238,13 +248,19 @@ class Atomwise(nn.Module):
         if not h.is_cuda:
             raise GotenNetHipError("gotennet_amd.outputs.Atomwise runs on a ROCm device only")
         n_mol = int(batch[-1].item()) + 1 if batch.numel() else 0
-        y = _AtomwiseFn.apply(h, self, z.to(torch.int32), molecule_ptr(batch, n_mol), n_mol)
+        params = list(self.parameters()) if (self.parameter_grads and torch.is_grad_enabled()) else []
+        if any(p.requires_grad for p in params):
+            y = _AtomwiseParamFn.apply(h, self, z.to(torch.int32), molecule_ptr(batch, n_mol), n_mol, *params)
+        else:
+            y = _AtomwiseFn.apply(h, self, z.to(torch.int32), molecule_ptr(batch, n_mol), n_mol)
         result = {self.property: y}                  # [n_mol,1], or the per-atom values [N,1] for aggregation_mode=None
         if self.contributions:
             result[self.contributions] = self._last_y.reshape(-1, getattr(self, "n_out", 1))
         if self.derivative:
             sign = -1.0 if self.negative_dr else 1.0
-            (dy,) = torch.autograd.grad(outputs=y, inputs=[pos], grad_outputs=torch.ones_like(y), retain_graph=True)
+            from .gotennet import positions_only
+            with positions_only(y):                  # parameter-gradient Functions on the way compute dL/dpos only
+                (dy,) = torch.autograd.grad(outputs=y, inputs=[pos], grad_outputs=torch.ones_like(y), retain_graph=True)
             result[self.derivative] = sign * dy
         return result
 
@@ -277,11 +293,12 @@ class AtomwiseV3(Atomwise):
         c = dict(c, scale=f(self.stddev), shift=0.0, mol_shift=f(self.mean))
         return layers, c
 
-    def energy_raw(self, h, z32, mol_ptr, n_mol, raw: bool = False, mode: Optional[str] = None):
+    def energy_raw(self, h, z32, mol_ptr, n_mol, raw: bool = False, mode: Optional[str] = None,
+                   acts: Optional[list] = None):
         if self.aggregation_mode is None and not raw:        # y_n + mean per atom: every atom is its own segment
             N = h.shape[0]
             mol_ptr, n_mol = torch.arange(N + 1, dtype=torch.int32, device=h.device), N
-        return super().energy_raw(h, z32, mol_ptr, n_mol, raw=raw, mode=mode)
+        return super().energy_raw(h, z32, mol_ptr, n_mol, raw=raw, mode=mode, acts=acts)
 
     def _per_atom_property(self, e, y):
         return e.reshape(-1, 1)
@@ -310,6 +327,70 @@ class _AtomwiseFn(torch.autograd.Function):
         mp = ctx.mol_ptr.long()
         per_atom = torch.repeat_interleave(ge.reshape(-1), mp[1:] - mp[:-1])
         return gh * per_atom.unsqueeze(1), None, None, None, None
+
+
+class _AtomwiseParamFn(torch.autograd.Function):
+    """h, *parameters -> the head's property, with parameter gradients (``Atomwise.parameter_grads``).  With u the per-atom
+    upstream gradient of output o (for aggregation_mode="mean" including the mean's 1 / n) and a_k the activated output
+    of hidden layer k (a_-1 = h): dW_last[o] = sum_i u_i^o scale_o a_last(i), and every earlier layer takes
+    dW_k = g_k^T a_(k-1), db_k = sum_i g_k with g_k = dL/d pre_k."""
+
+    @staticmethod
+    def forward(ctx, h, head, z32, mol_ptr, n_mol, *params):
+        acts = []
+        ctx.gn_param_fn, ctx.gn_positions_only = True, False
+        hd = h.detach().contiguous()
+        layers, c = head._packed()
+        e, y, tape = head.energy_raw(hd, z32, mol_ptr, n_mol, acts=acts)
+        head._last_y = y
+        ctx.state = (head, mol_ptr, hd, tape, acts, layers, c, params)
+        return head._per_atom_property(e, y) if head.aggregation_mode is None else e
+
+    @staticmethod
+    def backward(ctx, ge):
+        from .gotennet import refuse_second_order
+        refuse_second_order("Atomwise.parameter_grads")
+        head, mol_ptr, h, tape, acts, layers, c, params = ctx.state
+        pres, last_in, atom_scale = tape
+        N, Hd = last_in.shape
+        n_out = getattr(head, "n_out", 1)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=h.device)
+        u = ge.reshape(-1, n_out).to(torch.float32)
+        if head.aggregation_mode is not None and u.shape[0] != N:
+            mp = mol_ptr.long()
+            u = torch.repeat_interleave(u, mp[1:] - mp[:-1], dim=0)
+        if atom_scale is not None:
+            u = u * atom_scale.unsqueeze(1)
+        scales = c["scales"] if n_out > 1 else [c["scale"]]
+        U = (u * torch.tensor(scales, dtype=torch.float32, device=h.device)).contiguous()
+        weights = not ctx.gn_positions_only          # False inside positions_only(): dL/dh alone
+        grads = {id(d.weight): torch.empty_like(d.weight) for d in layers}
+        grads.update({id(d.bias): torch.empty_like(d.bias) for d in layers})
+        a_last = acts[-1] if acts else h
+        probs = [dict(dY=U, ldy=n_out, A=a_last, lda=Hd, dW=grads[id(layers[-1].weight)], db=grads[id(layers[-1].bias)],
+                      rows=N, nout=n_out, K=Hd)]
+        # g = dL/d pre_last (dL/dh without hidden layers): sum_o u^o scale_o W_o act'(pre_last)
+        act_last = head.act_kind if pres else 11
+        g, part = new(N, Hd), new(N, Hd)
+        for o in range(n_out):
+            w_o = c["w_rows"][o] if n_out > 1 else c["w"][-1]
+            call("gn_head_grad", ptr(last_in), ptr(w_o), scales[o], ptr(u[:, o].contiguous()), N, Hd,
+                 ptr(g if o == 0 else part), act_last, engine._stream())
+            if o:
+                g.add_(part)
+        for k in range(len(pres) - 1, -1, -1):       # g = dL/d pre_k
+            d = layers[k]
+            probs.append(dict(dY=g, ldy=d.out_features, A=acts[k - 1] if k > 0 else h, lda=d.in_features,
+                              dW=grads[id(d.weight)], db=grads[id(d.bias)], rows=N, nout=d.out_features, K=d.in_features))
+            gi = new(N, d.in_features)
+            engine.gemm(g, d.out_features, c["wt"][k], None, gi, d.in_features, N, d.in_features, d.out_features,
+                        dgate=pres[k - 1] if k > 0 else None, kind=head.act_kind)
+            g = gi
+        if not weights:
+            return (g if ctx.needs_input_grad[0] else None, None, None, None, None, *([None] * len(params)))
+        engine.weight_grad_group(probs)
+        pg = [grads.get(id(p)) if ctx.needs_input_grad[5 + i] else None for i, p in enumerate(params)]
+        return (g if ctx.needs_input_grad[0] else None, None, None, None, None, *pg)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -405,7 +486,8 @@ def _field(inputs, name):
 class Dipole(nn.Module):
     """Reference outputs.py:379-468: two GatedEquivariantBlocks on (h, X[:, :3]) -> atomic dipoles + charges,
     ``y = sum_atoms (mu_n + pos_n q_n)`` per molecule (its norm with ``predict_magnitude``).  ``mean`` / ``stddev`` are
-    plain attributes like in the reference (not in the state_dict).  Inference only (the QM9 task takes no derivative)."""
+    plain attributes like in the reference (not in the state_dict).  Inference only (the QM9 task takes no derivative); its
+    parameters are not trained on the accelerated path (no parameter gradients)."""
 
     def __init__(self, n_in: int, n_hidden: Optional[int] = None, activation=F.silu, property: str = "dipole",
                  predict_magnitude: bool = False, output_v: bool = True, mean=None, stddev=None):
@@ -453,7 +535,8 @@ _ATOMIC_MASS = [1.0, 1.008, 4.002602, 6.94, 9.0121831, 10.81, 12.011, 14.007, 15
 
 class ElectronicSpatialExtentV2(Atomwise):
     """Reference outputs.py:471-545: ``y = sum_atoms |pos_n - c|^2 x_n`` with ``x = out_net(h)`` (the raw MLP output:
-    the reference does not standardise here) and ``c`` the mass-weighted centroid of the molecule."""
+    the reference does not standardise here) and ``c`` the mass-weighted centroid of the molecule.  Inference only: its
+    parameters are not trained on the accelerated path (``parameter_grads`` is not honoured here)."""
 
     def __init__(self, n_in: int, n_layers: int = 2, n_hidden: Optional[int] = None, activation=shifted_softplus,
                  property: str = "y", contributions: Optional[str] = None, mean=None, stddev=None, outnet=None,

@@ -38,7 +38,7 @@ extern "C" {
 
 #define GN_OK 0
 #define GN_ERR_BAD_ARG 10001     /* shape/flag combination the kernels do not implement */
-#define GN_ABI_VERSION 8
+#define GN_ABI_VERSION 9
 /* OR-ed into the `lmax` ARGUMENT of gn_message_aggregate, gn_message_backward(_groups), gn_htr_edge and
  * gn_htr_backward: run this call on the degree-sliced kernel family at lmax <= 4 as well (the family that serves
  * lmax 5..8).  An explicit per-call request -- the library reads no environment variable and keeps no switch; every
@@ -431,6 +431,43 @@ int gn_radius_fill(const float* pos, const int64_t* batch, int N, float cutoff, 
  * gn_radius_fill, so a replayed step is bit-identical to an eager one on the same edge list. */
 int gn_edge_vectors(const float* pos, const int* src, const int* dst, int E, float* edge_vec, float* edge_diff,
                     void* stream);
+
+/* ---- parameter gradients (first-order training: a loss on energies and / or (h, X)) -------------
+ * Every reduction below runs in a fixed order and uses no atomics: identical inputs give identical bits. */
+/* dW = dY^T A and db = sum_r dY of a Dense product y = A W^T + b (layers.py:457-529): several independent problems in
+ * one launch.  dW[n * ldw + k] = sum_{r < rows} dY[row(r), y_off + n] A[row(r), a_off + k] and, when db != NULL,
+ * db[n] = sum_r dY[row(r), y_off + n]; row(r) = (r / row_cnt) * row_gstride + row_goff + r % row_cnt is the row map of
+ * gn_gemm_desc and addresses both operands (per-degree W_vk_l rows of X [N, D, F]; (1, 1, 0) = every row).  Any
+ * rows >= 0 (0 writes zeros), nout >= 1, K >= 1.  Exact fp32 (v_mfma_f32_32x32x2_f32, fp32 accumulation) whatever
+ * the projection arithmetic of the model: both operands are run-time activations.  The rows are split across
+ * workgroups by the problem shape alone; the partial tiles go to the caller's workspace (gn_weight_grad_workspace
+ * floats for the same problems) and are summed in split order; dW and db are overwritten. */
+typedef struct gn_wgrad_desc {
+    const float* dY; int ldy; int y_off;
+    const float* A; int lda; int a_off;
+    float* dW; int ldw;
+    float* db;
+    int rows, nout, K;
+    int row_cnt, row_gstride, row_goff;
+} gn_wgrad_desc;
+long gn_weight_grad_workspace(const gn_wgrad_desc* problems, int n);
+int gn_weight_grad_group(const gn_wgrad_desc* problems, int n, float* work, long work_floats, void* stream);
+/* Embedding gradients of NodeInit (layers.py:1658-1675; gotennet.py:969-975):
+ * dA_na[s] = sum_{i: z_i = s} g_ctx[i, 0:F] (row 0, the padding_idx, is zero);
+ * dA_nbr[s] = sum over the non-self-loop edges e = (j -> i) with z_j = s of g_ctx[i, F:2F] feat[e, 0:F] cut[e]: first per
+ * source atom j over the by-source view (colptr / perm of gn_build_csc, into work [N, F]), then per species.
+ * order [N]: a stable argsort of z; sp_ptr [n_species + 1]: the first sorted position of each species (host plumbing).
+ * Species without atoms get zero rows. */
+int gn_embedding_grad(const float* g_ctx, const float* feat, int ldf, const float* cut, const int* dst,
+                      const int* colptr, const int* perm, const int* order, const int* sp_ptr, int n_species,
+                      int N, int F, float* work, float* dA_na, float* dA_nbr, void* stream);
+/* LayerNorm affine gradients (layers.py:518-529, gotennet.py:315, 397): dgamma[c] = sum_r g_z[r,c] x_hat[r,c],
+ * dbeta[c] = sum_r g_z[r,c] with g_z = g_out * act'(x_hat gamma + beta) (act: the activation after the norm, as in
+ * gn_layernorm_silu; GN_ACT_NONE for a bare nn.LayerNorm).  x [N, C] is the un-normalised input.  Two stages: 64-row
+ * partials in work (gn_layernorm_param_grad_workspace floats), then a column sum in chunk order. */
+long gn_layernorm_param_grad_workspace(int N, int C);
+int gn_layernorm_param_grad(const float* x, const float* gamma, const float* beta, float eps, const float* g_out,
+                            int N, int C, int act, float* work, float* dgamma, float* dbeta, void* stream);
 
 
 #ifdef __cplusplus
