@@ -104,7 +104,7 @@ def embed_pack(pw: "engine.PackedWeights", F: int, H: int, M: int) -> "engine.Pa
         nl.Wvu = e(lw.Wvu, 1, 1)
         nl.Wm0, nl.bm0 = e(lw.Wm0, 1, 2), e(lw.bm0, 1, 0)
         nl.Wm1, nl.bm1 = e(lw.Wm1, 2, 1), e(lw.bm1, 2, 0)
-        # the GATA input norms (layernorm / steerable_norm) run on the COMPACT real channels (engine._input_norms): their
+        # the GATA input norms (layernorm / steerable_norm) run on the COMPACT real channels (engine._norm_h / _norm_X and their _backward twins, given ``emb_idx``): their
         # parameters stay in the model's own layout
         nl.ln_w, nl.ln_b, nl.tln_w = lw.ln_w, lw.ln_b, lw.tln_w
         if lw.Wt is not None:

@@ -18,7 +18,7 @@ from __future__ import annotations
 import dataclasses
 import os
 from dataclasses import dataclass, field
-from typing import List, Optional, Tuple
+from typing import Any, List, Optional
 
 import torch
 
@@ -28,11 +28,11 @@ from ._lib import call, ptr
 
 @dataclass
 class LayerWeights:
-    Wn1: torch.Tensor; bn1: torch.Tensor          # [W_q; W_k; gamma_s.0; gamma_v.0]  [4F, F]
-    Ws2: torch.Tensor; bs2: torch.Tensor          # gamma_s.1 [MF, F]
-    Wv2: torch.Tensor; bv2: torch.Tensor          # gamma_v.1 [MF, F]
-    We: torch.Tensor; be: torch.Tensor            # [W_re; W_rs] [(1+M)F, F]
-    Wvu: Optional[torch.Tensor] = None                                         # EQFF (None in a stand-alone GATA pack)
+    Wn1: Optional[torch.Tensor] = None; bn1: Optional[torch.Tensor] = None   # [W_q; W_k; gamma_s.0; gamma_v.0]  [4F, F]
+    Ws2: Optional[torch.Tensor] = None; bs2: Optional[torch.Tensor] = None   # gamma_s.1 [MF, F]
+    Wv2: Optional[torch.Tensor] = None; bv2: Optional[torch.Tensor] = None   # gamma_v.1 [MF, F]
+    We: Optional[torch.Tensor] = None; be: Optional[torch.Tensor] = None     # [W_re; W_rs] [(1+M)F, F]
+    Wvu: Optional[torch.Tensor] = None              # EQFF (None in a stand-alone GATA pack, whose GATA operands above are None)
     Wm0: Optional[torch.Tensor] = None; bm0: Optional[torch.Tensor] = None
     Wm1: Optional[torch.Tensor] = None; bm1: Optional[torch.Tensor] = None
     Wt: Optional[torch.Tensor] = None; bt: Optional[torch.Tensor] = None   # gamma_t
@@ -45,10 +45,7 @@ class LayerWeights:
     t_ln_w: Optional[torch.Tensor] = None; t_ln_b: Optional[torch.Tensor] = None   # its LayerNorm (edge_ln)
     Wedp: Optional[torch.Tensor] = None; bedp: Optional[torch.Tensor] = None   # W_edp
     w_ln_w: Optional[torch.Tensor] = None; w_ln_b: Optional[torch.Tensor] = None   # LayerNorm before / after W_edp
-    # prefixes for the first interaction (X_in = 0: no tensor-gate blocks), views made on first use
-    We0: Optional[torch.Tensor] = None; be0: Optional[torch.Tensor] = None
-    Ws20: Optional[torch.Tensor] = None; Wv20: Optional[torch.Tensor] = None
-    T: dict = field(default_factory=dict)         # lazily built transposes for the backward
+    T: dict = field(default_factory=dict)         # derived operands (``derived``): prefix views, transposes, concatenations
 
 
 @dataclass
@@ -59,7 +56,7 @@ class PackedWeights:
     Wb: torch.Tensor; bb: torch.Tensor
     rb0: torch.Tensor; rb1: torch.Tensor          # radial-basis parameter vectors (means/betas, freqs, offsets/widths)
     layers: List[LayerWeights] = field(default_factory=list)
-    T: dict = field(default_factory=dict)
+    T: dict = field(default_factory=dict)         # derived operands (``derived``)
     emb_idx: Optional[torch.Tensor] = None        # model embedded in a power-of-two width (embed.py): real channel f sits at emb_idx[f]
     F_model: int = 0                              # ... and its real width (0: not embedded)
 
@@ -79,47 +76,28 @@ def zero_X_in(cfg: "Config", li: int) -> bool:
             and cfg.aggr == 0 and not cfg.wide)
 
 
-def _We_first(cfg: "Config", lw) -> Tuple[torch.Tensor, torch.Tensor, int]:
-    """Rows of [W_re; W_rs] without the tensor-gate blocks (a prefix: attention, scalar, direction gates)."""
-    n0 = (2 + (cfg.lmax if cfg.sep_dir else 1)) * cfg.F
-    if lw.We0 is None:
-        lw.We0, lw.be0 = lw.We[:n0], (lw.be[:n0] if lw.be is not None else None)
-    return lw.We0, lw.be0, n0
-
-
-def _value_first(cfg: "Config", lw) -> int:
-    """Rows of gamma_s.1 / gamma_v.1 without the tensor-gate blocks (a prefix: scalar, direction gates)."""
-    n0 = (1 + (cfg.lmax if cfg.sep_dir else 1)) * cfg.F
-    if lw.Ws20 is None:
-        lw.Ws20, lw.Wv20 = lw.Ws2[:n0], lw.Wv2[:n0]
-    return n0
-
-
-def _Tqk(lw) -> torch.Tensor:
-    """Transposed q | k rows of W_n1 ([F, 2F]) for the input-gradient product, cached."""
-    t = lw.T.get("Wn1_qk")
+def derived(holder, key, build):
+    """The operand ``key`` derived from the weights of ``holder`` (a LayerWeights or PackedWeights), kept in ``holder.T``: ONE
+    object per pack (``split_weight`` caches the planes ON the tensor object), made by ``build()`` inside the call that first
+    needs it (pipeline.InFlight fences only the first call of a kind per pack), never ahead of it (inference pays for no transposes)."""
+    t = holder.T.get(key)
     if t is None:
-        F2 = lw.Wn1.shape[0] // 2
-        t = lw.T["Wn1_qk"] = lw.Wn1[:F2].t().contiguous()
+        t = holder.T[key] = build()
     return t
 
 
-def _Tsv(lw) -> torch.Tensor:
-    """Transposed gamma_s.0 | gamma_v.0 rows of W_n1 ([F, 2F]), cached."""
-    t = lw.T.get("Wn1_sv")
-    if t is None:
-        F2 = lw.Wn1.shape[0] // 2
-        t = lw.T["Wn1_sv"] = lw.Wn1[F2:].t().contiguous()
-    return t
+def _T(holder, name: str, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+    """Transposed copy of the operand ``name`` -- of its rows [lo, hi) -- ([in, out] -> the GEMM's [out', in'] layout for
+    input-gradients).  (Fifty look-ups per one-molecule step: the hit does not go through ``derived``.)"""
+    key = name if hi is None else (name, lo, hi)
+    t = holder.T.get(key)
+    return t if t is not None else derived(holder, key, lambda: getattr(holder, name)[lo:hi].t().contiguous())
 
 
-def _T(holder, name: str) -> torch.Tensor:
-    """Transposed copy ([in, out] -> the GEMM's [out', in'] layout for input-gradients), cached."""
-    t = holder.T.get(name)
-    if t is None:
-        t = getattr(holder, name).t().contiguous()
-        holder.T[name] = t
-    return t
+def _rows(lw, name: str, n: int) -> torch.Tensor:
+    """The first ``n`` rows of the operand ``name`` (a view): what a zero-X_in layer uses of [W_re; W_rs], gamma_s.1 and
+    gamma_v.1 -- a prefix without the tensor-gate blocks (``_Call.cols``)."""
+    return derived(lw, ("rows", name, n), lambda: getattr(lw, name)[:n])
 
 
 @dataclass
@@ -160,6 +138,20 @@ class Config:
     def D(self) -> int:
         return (self.lmax + 1) ** 2 - 1
 
+    def degree_blocks(self, N: int, explicit: bool = False):
+        """The row blocks of an [N, D, F] tensor that the weights ``lw.Wvk`` act on: -> [(index into Wvk, rows, rowmap)],
+        rowmap = (cnt, D, off): one per degree l (cnt = 2l + 1 rows per atom from row off), or with ONE shared weight
+        (sep_htr=False: ``htr_mode & 1``) every row -- the identity, which ``explicit`` writes (D, D, 0) as the X-products
+        backward always has and else is the default (1, 1, 0): equivalent, historical, kept so no descriptor changes."""
+        D = self.D
+        if self.htr_mode & 1:
+            return [(0, N * D, (D, D, 0) if explicit else (1, 1, 0))]
+        blocks, off = [], 0
+        for l in range(1, self.lmax + 1):
+            blocks.append((l - 1, N * (2 * l + 1), (2 * l + 1, D, off)))
+            off += 2 * l + 1
+        return blocks
+
     @property
     def lmax_arg(self) -> int:
         """The ``lmax`` argument of the message / HTR entry points: GN_LMAX_SLICED rides in it."""
@@ -199,7 +191,7 @@ def _stream() -> int:
 
 #: DEFAULT projection arithmetic of a model that does not choose one (``GotenNet.gemm_mode = None``; env GN_GEMM_MODE
 #: sets the default at import; every GPU parity test runs in all three).  The arithmetic and the activation kind of a
-#: call are carried by ``Config`` (``cfg.gemm_mode``, ``cfg.act``) and bound per call by ``_Proj`` -- there is no
+#: call are carried by ``Config`` (``cfg.gemm_mode``, ``cfg.act``) and bound per call by ``_Call`` -- there is no
 #: per-call module state, so two models with different arithmetics can run from two threads.
 #:   "f16x2" (default) -- every fp32 operand as two fp16 planes scaled by block exponents (A: per staging wave and
 #:       32-column K-slab = 16 or 32 neighbouring rows of the workgroup tile, running maximum, accumulators rescaled when
@@ -293,12 +285,21 @@ def gemm_group(problems, mode=None, kind=None):
         call(_PLANE_MODES[mode][1] if split else "gn_gemm_group", arr, len(chunk), _stream())
 
 
-class _Proj:
-    """The projection launchers bound to ONE model's arithmetic and activation kind (``cfg.gemm_mode``, ``cfg.act``)."""
-    __slots__ = ("mode", "act")
+class _Call:
+    """What ONE forward / backward / stand-alone layer call binds, evaluated once (a one-molecule eager step is host-bound):
+    the projection launchers with the model's arithmetic and activation kind (``cfg.gemm_mode``, ``cfg.act``), the
+    configuration, the graph, the stream, the sizes, the degree blocks and the gate columns ``cols[first]``."""
+    __slots__ = ("mode", "act", "cfg", "g", "st", "N", "E", "F", "D", "Fe", "lde", "blocks", "cols")
 
-    def __init__(self, cfg: "Config"):
-        self.mode, self.act = resolve_mode(cfg.gemm_mode), cfg.act
+    def __init__(self, cfg: "Config", g: Optional["Graph"] = None, explicit_blocks: bool = False):
+        self.mode, self.act, self.cfg, self.g, self.st = resolve_mode(cfg.gemm_mode), cfg.act, cfg, g, _stream()
+        self.F, self.D, self.Fe, self.lde = cfg.F, cfg.D, cfg.Fe, (1 + cfg.M) * cfg.F
+        # columns of (the edge projection [W_re; W_rs], gamma_s.1 / gamma_v.1) a layer computes: attention (edge only), scalar,
+        # direction and tensor gates; cols[True]: a first interaction (X_in = 0) -- no tensor gates, a prefix
+        n = cfg.lmax if cfg.sep_dir else 1
+        self.cols = ((self.lde, cfg.M * cfg.F), ((2 + n) * cfg.F, (1 + n) * cfg.F))
+        self.N, self.E = (g.N, g.E) if g is not None else (None, None)      # (no graph: the node-local EQFF layer)
+        self.blocks = cfg.degree_blocks(g.N, explicit_blocks) if g is not None else None
 
     def gemm(self, *args, **kw):
         kw.setdefault("kind", self.act)
@@ -392,6 +393,8 @@ class Graph:
 
 @dataclass
 class LayerTape:
+    """What one layer of ``forward`` writes: a saving forward keeps one per layer (the tape), inference reuses one as scratch."""
+    first: bool = False     # forward's ``zero_X_in`` decision, which backward reads: zero-X_in kernels; X_in, X_raw stay None
     h_in: torch.Tensor = None; X_in: torch.Tensor = None; t_in: torch.Tensor = None
     nproj: torch.Tensor = None; xs: torch.Tensor = None; vs: torch.Tensor = None
     eproj: torch.Tensor = None; attn: torch.Tensor = None
@@ -436,148 +439,215 @@ def param_grad_config(cfg: Config) -> Config:
     return dataclasses.replace(cfg, fuse_eqff=False)
 
 
-def _forward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, save: bool = False,
+def _norm_h(lw: LayerWeights, h: torch.Tensor, emb_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.LayerNorm on h at the GATA input (gotennet.py:397).  ``emb_idx`` (embedded model, embed.py): over the real
+    channels -- gathered to a compact tensor for the kernel, scattered back into a zero-padded one."""
+    x = h if emb_idx is None else h.index_select(1, emb_idx)
+    y = torch.empty_like(x)
+    call("gn_layernorm", ptr(x), ptr(lw.ln_w), ptr(lw.ln_b), 1e-5, x.shape[0], x.shape[1], ptr(y), _stream())
+    return y if emb_idx is None else torch.zeros_like(h).index_copy_(1, emb_idx, y)
+
+
+def _norm_X(lw: LayerWeights, X: torch.Tensor, lmax: int, emb_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """TensorLayerNorm on X at the GATA input (gotennet.py:398, layers.py:1497-1563); ``emb_idx`` as in ``_norm_h``."""
+    x = X if emb_idx is None else X.index_select(2, emb_idx)
+    y = torch.empty_like(x)
+    call("gn_tensor_norm", ptr(x), ptr(lw.tln_w), 1e-12, x.shape[0], x.shape[2], lmax, ptr(y), _stream())
+    return y if emb_idx is None else torch.zeros_like(X).index_copy_(2, emb_idx, y)
+
+
+def _norm_h_backward(lw: LayerWeights, h_raw, g_y, g_x, emb_idx: Optional[torch.Tensor] = None):
+    """g_x = dL/dh of ``_norm_h`` given g_y = dL/d of its output (embedded: compact -> kernel -> padded layout)."""
+    x, gy, gx = h_raw, g_y, g_x
+    if emb_idx is not None:                        # (named: alive until the launch)
+        x, gy = h_raw.index_select(1, emb_idx), g_y.index_select(1, emb_idx)
+        gx = torch.empty_like(gy)
+    call("gn_layernorm_backward", ptr(x), ptr(lw.ln_w), 1e-5, ptr(gy), x.shape[0], x.shape[1], ptr(gx), _stream())
+    if emb_idx is not None:
+        g_x.zero_().index_copy_(1, emb_idx, gx)
+
+
+def _norm_X_backward(lw: LayerWeights, X_raw, g_y, g_x, lmax: int, emb_idx: Optional[torch.Tensor] = None):
+    """g_x = dL/dX of ``_norm_X`` given g_y = dL/d of its output."""
+    x, gy, gx = X_raw, g_y, g_x
+    if emb_idx is not None:
+        x, gy = X_raw.index_select(2, emb_idx), g_y.index_select(2, emb_idx)
+        gx = torch.empty_like(gy)
+    call("gn_tensor_norm_backward", ptr(x), ptr(lw.tln_w), ptr(gy), 1e-12, x.shape[0], x.shape[2], lmax, ptr(gx), _stream())
+    if emb_idx is not None:
+        g_x.zero_().index_copy_(2, emb_idx, gx)
+
+
+def gata_input_norms(cfg: Config, lw: LayerWeights, h: torch.Tensor, X: torch.Tensor):
+    """The optional input norms of a GATA layer (gotennet.py:397-398) on their own: -> (h or LN(h), X or TLN(X))."""
+    N = h.shape[0]
+    return (_norm_h(lw, h) if cfg.layernorm and N else h), (_norm_X(lw, X, cfg.lmax) if cfg.steerable_norm and N else X)
+
+
+def _htr_problems(p: _Call, lw: LayerWeights, X, EQ, EK):
+    """EQ = X W_vq^T and the per-degree EK_l = X_l W_vk_l^T of the HTR edge weights (gotennet.py:561-611)."""
+    F_, Fe, N = p.F, p.Fe, p.N
+    return [dict(A=X, lda=F_, W=lw.Wvq, C=EQ, ldc=Fe, rows=N * p.D, nout=Fe, K=F_)] + [
+        dict(A=X, lda=F_, W=lw.Wvk[k], C=EK, ldc=Fe, rows=rows, nout=Fe, K=F_, rowmap=rowmap)
+        for k, rows, rowmap in p.blocks]
+
+
+def _init_forward(p: _Call, pw: PackedWeights, z32, new, tape: Optional[Tape], pgrads: bool):
+    """NodeInit and EdgeInit (gotennet.py:973-977): -> (h [N,F], t [E,F]); fills the init fields of ``tape``."""
+    cfg, g, st, F_, R, N, E, gemm = p.cfg, p.g, p.st, p.F, p.cfg.R, p.N, p.E, p.gemm
+    feat = new(E, 2 * F_)
+    gemm(g.phi, R, pw.Winit, pw.binit, feat, 2 * F_, E, 2 * F_, R)
+    ctx0 = new(N, 2 * F_)
+    call("gn_node_init", ptr(z32), ptr(g.rowptr), ptr(g.src), ptr(feat), 2 * F_, ptr(g.cut),
+         ptr(pw.A_na), ptr(pw.A_nbr), N, F_, ptr(ctx0), st)
+    Fc = cfg.Fc or F_                              # (an embedded model keeps this intermediate compact: LayerNorm over the real channels)
+    y_pre = new(N, Fc)
+    gemm(ctx0, 2 * F_, pw.Wa, pw.ba, y_pre, Fc, N, Fc, 2 * F_)
+    y = new(N, Fc)
+    call("gn_layernorm_silu", ptr(y_pre), ptr(pw.ln_w), ptr(pw.ln_b), 1e-5, N, Fc, ptr(y), cfg.act, st)
+    h = new(N, F_)
+    gemm(y, Fc, pw.Wb, pw.bb, h, F_, N, F_, Fc)
+    t = new(E, F_)
+    call("gn_edge_init", ptr(h), ptr(g.rowptr), ptr(g.src), feat.data_ptr() + 4 * F_, 2 * F_, N, F_, ptr(t), st)
+    if tape is not None:
+        tape.feat, tape.y_pre, tape.h0 = feat, y_pre, h
+        if pgrads:
+            tape.ctx0, tape.y = ctx0, y
+    return h, t
+
+
+def _layer_buffers(cfg: Config, N: int, E: int, new, last: bool, save: bool, pgrads: bool = False):
+    """-> (LayerTape with the buffers one layer of ``forward`` writes, h2, X2, t2 for its outputs).  A saving forward makes
+    them per layer; inference once (``last=False``: the widest set), the outputs ping-ponging against the inputs.  Pre-
+    activation copies exist only when saving; ``nact`` / ``g1act`` are the caller's shared scratch unless ``pgrads``."""
+    F_, D, M, Fe = cfg.F, cfg.D, cfg.M, cfg.Fe
+    lt = LayerTape(xs=new(N, M * F_), vs=new(N, M * F_), eproj=new(E, (1 + M) * F_), attn=new(E, cfg.H),
+                   Xp=new(N, D, F_), ctx=new(N, 2 * F_), mm=new(N, 2 * F_))
+    if save:
+        lt.nproj, lt.pre_g1 = new(N, 4 * F_), new(N, F_)
+    if not last:
+        lt.EQ, lt.EK, lt.w = new(N, D, Fe), new(N, D, Fe), new(E, Fe)
+        if save:
+            lt.pre_t = new(E, F_)
+            lt.w_raw = new(E, Fe) if (cfg.htr_mode >> 2) else None
+    if pgrads:                                     # activated copies: one per layer instead of the shared scratch
+        lt.nact, lt.g1act = new(N, 4 * F_), new(N, F_)
+    return lt, new(N, F_), new(N, D, F_), (None if last else new(E, F_))
+
+
+def _gata_forward(p: _Call, lw: LayerWeights, lt: LayerTape, nact, h, X, t, h2, X2):
+    """GATA projections (gotennet.py:400-407) and message stage (452-559, 613-640, 426-427: scores + segment softmax,
+    message, aggregate, residual) of one layer: writes h2, X2, ``nact`` and lt.xs, vs, eproj, attn -- and the pre-activation
+    copy lt.nproj, where it is not None.  ``lt.first``: X is the zero tensor, no tensor-gate blocks."""
+    cfg, g, st, F_, lde, N, E, first = p.cfg, p.g, p.st, p.F, p.lde, p.N, p.E, lt.first
+    H, M, xs, vs, eproj, attn = cfg.H, cfg.M, lt.xs, lt.vs, lt.eproj, lt.attn
+    ne, nv = p.cols[first]
+    # The atom-sized node projection rides in the edge projection's launch (its 168 tiles fill the tail of the 5100-tile
+    # grid).  SiLU of the two hidden blocks is applied ONCE by the epilogue (a SiLU prologue in the two products below would
+    # redo it for each of their 4M column tiles); the pre-activation copy is what the backward needs.
+    p.group([dict(A=t, lda=F_, W=_rows(lw, "We", ne) if first else lw.We, bias=lw.be, C=eproj, ldc=lde, rows=E, nout=ne, K=F_),
+             dict(A=h, lda=F_, W=lw.Wn1, bias=lw.bn1, C=nact, ldc=4 * F_, rows=N, nout=4 * F_, K=F_,
+                  act=(2 * F_, 4 * F_), pre_out=lt.nproj)])
+    p.group([dict(A=nact, lda=4 * F_, W=_rows(lw, "Ws2", nv) if first else lw.Ws2, bias=lw.bs2, C=xs, ldc=M * F_, rows=N,
+                  nout=nv, K=F_, a_off=2 * F_),
+             dict(A=nact, lda=4 * F_, W=_rows(lw, "Wv2", nv) if first else lw.Wv2, bias=lw.bv2, C=vs, ldc=M * F_, rows=N,
+                  nout=nv, K=F_, a_off=3 * F_)])
+    # q | k are columns [0, 2F) of nact; t_attn (pre-activation) columns [0, F) of eproj, t_filter the rest
+    call("gn_attn_softmax", ptr(nact), nact.data_ptr() + 4 * F_, 4 * F_, ptr(eproj), lde,
+         ptr(g.rowptr), ptr(g.src), ptr(g.outdeg), N, F_, H, ptr(attn), cfg.act, st)
+    call("gn_message_aggregate", ptr(xs), ptr(vs), M * F_, eproj.data_ptr() + 4 * F_, lde,
+         ptr(attn), ptr(g.rl), ptr(g.cut), ptr(g.rowptr), ptr(g.src), ptr(h), None if first else ptr(X), ptr(h2), ptr(X2),
+         N, F_, H, cfg.lmax_arg_msg, int(cfg.sep_dir), int(cfg.sep_tensor), st)
+
+
+def _eqff_htr_forward(p: _Call, lw: LayerWeights, lt: LayerTape, g1act, h, X, t, t2, save: bool, eq_fused: bool):
+    """X-products, EQFF (gotennet.py:731-746: h, X updated in place) and HTR edge weights + edge update (561-611: t2, where
+    the layer has one) of one layer, on the message stage's h, X."""
+    cfg, g, st, F_, D, Fe, N, E = p.cfg, p.g, p.st, p.F, p.D, p.Fe, p.N, p.E
+    last, Xp, ctx, mm = lw.Wt is None, lt.Xp, lt.ctx, lt.mm
+    # every product of the updated X (X W_vu^T for EQFF; EQ and the per-degree EK_l for HTR) in one launch
+    xprods = [dict(A=X, lda=F_, W=lw.Wvu, C=Xp, ldc=F_, rows=N * D, nout=F_, K=F_)]
+    if not last:
+        xprods += _htr_problems(p, lw, X, lt.EQ, lt.EK)
+    p.group(xprods)
+    # Where covered the EQFF chain after X_p is ONE kernel (context, both gamma_m layers, update); else: context kernel, the
+    # first gamma_m layer riding in the launch of the edge-sized gamma_t product, the second layer, update kernel
+    m0 = None
+    if eq_fused:
+        call("gn_eqff_fused_forward", ptr(Xp), ptr(split_weight(lw.Wm0, p.mode)), ptr(lw.bm0),
+             ptr(split_weight(lw.Wm1, p.mode)), ptr(lw.bm1), float(cfg.eps), N, F_, D, ptr(h), ptr(X),
+             ptr(ctx) if save else None, ptr(lt.pre_g1), ptr(mm) if save else None, 1 if p.mode == "split" else 2, st)
+    else:
+        call("gn_eqff_context", ptr(h), ptr(Xp), float(cfg.eps), N, F_, D, ptr(ctx), st)
+        m0 = dict(A=ctx, lda=2 * F_, W=lw.Wm0, bias=lw.bm0, C=g1act, ldc=F_, rows=N, nout=F_, K=2 * F_, act=(0, F_),
+                  pre_out=lt.pre_g1)
+    if last:
+        p.group([m0])
+    else:
+        call("gn_htr_edge", ptr(lt.EQ), ptr(lt.EK), ptr(g.rl), ptr(g.rowptr), ptr(g.src), N, Fe, cfg.lmax_arg, cfg.htr_mode,
+             ptr(lt.w_raw), ptr(lt.w), st)
+        if cfg.composed_update:
+            upd = _edge_update_composed(cfg, lw, t, lt.w, t2, E, lt.pre_t)
+            if save:
+                lt.upd = upd
+            p.group([m0])
+        else:
+            p.group([dict(A=t, lda=F_, W=lw.Wt, bias=lw.bt, C=t2, ldc=F_, rows=E, nout=F_, K=F_, act=(0, F_), res=t,
+                          gate=lt.w, pre_out=lt.pre_t), m0])
+    if not eq_fused:
+        p.gemm(g1act, F_, lw.Wm1, lw.bm1, mm, 2 * F_, N, 2 * F_, F_)
+        call("gn_eqff_update", ptr(mm), ptr(Xp), N, F_, D, ptr(h), ptr(X), st)
+
+
+def forward(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, save: bool = False,
             trace: Optional[list] = None, pgrads: bool = False):
     """-> (h [N,F], X [N,D,F], tape or None).  ``save`` keeps what ``backward`` needs; ``pgrads`` (with ``save``, and a
     ``param_grad_config``) also keeps the inputs of every projection for the parameter gradients;
     ``trace`` (tests only) collects per-layer clones of (h, X, t)."""
-    F_, R, H, D, M, lmax = cfg.F, cfg.R, cfg.H, cfg.D, cfg.M, cfg.lmax
-    Fe = cfg.Fe
-    N, E = g.N, g.E
+    F_, D, N, E = cfg.F, cfg.D, g.N, g.E
     if save:
         check_backward_supported(cfg)               # before any launch: a saving forward is only run for a backward
     if pgrads:
         check_param_grads_supported(cfg)
         if not save or cfg.fuse_eqff is not False:
             raise ValueError("internal: a parameter-gradient forward saves its tape and runs the un-fused EQFF chain")
-    proj = _Proj(cfg)
-    gemm, gemm_group = proj.gemm, proj.group
-    dev = z32.device
-    f32 = dict(dtype=torch.float32, device=dev)
+    p = _Call(cfg, g)
+    f32 = dict(dtype=torch.float32, device=z32.device)
     new = lambda *shape: torch.empty(shape, **f32)
     tape = Tape() if save else None
-
-    # ---- init (gotennet.py:973-977) -------------------------------------------------
-    feat = new(E, 2 * F_)
-    gemm(g.phi, R, pw.Winit, pw.binit, feat, 2 * F_, E, 2 * F_, R)
-    ctx0 = new(N, 2 * F_)
-    call("gn_node_init", ptr(z32), ptr(g.rowptr), ptr(g.src), ptr(feat), 2 * F_, ptr(g.cut),
-         ptr(pw.A_na), ptr(pw.A_nbr), N, F_, ptr(ctx0), _stream())
-    Fc = cfg.Fc or F_                              # (an embedded model keeps this intermediate compact: LayerNorm over the real channels)
-    y_pre = new(N, Fc)
-    gemm(ctx0, 2 * F_, pw.Wa, pw.ba, y_pre, Fc, N, Fc, 2 * F_)
-    y = new(N, Fc)
-    call("gn_layernorm_silu", ptr(y_pre), ptr(pw.ln_w), ptr(pw.ln_b), 1e-5, N, Fc, ptr(y), cfg.act, _stream())
-    h = new(N, F_)
-    gemm(y, Fc, pw.Wb, pw.bb, h, F_, N, F_, Fc)
-    t = new(E, F_)
-    call("gn_edge_init", ptr(h), ptr(g.rowptr), ptr(g.src), feat.data_ptr() + 4 * F_, 2 * F_, N, F_, ptr(t), _stream())
-    if save:
-        tape.feat, tape.y_pre, tape.h0 = feat, y_pre, h
-    if pgrads:
-        tape.ctx0, tape.y = ctx0, y
-
+    h, t = _init_forward(p, pw, z32, new, tape, pgrads)
     # gotennet.py:992: X starts as the zero tensor.  Where the first interaction runs the zero-X_in kernels nothing ever reads
     # it (message stage and message backward get a null X_in): no fill launch
     X = new(N, D, F_) if (zero_X_in(cfg, 0) and pw.layers) else torch.zeros((N, D, F_), **f32)
-    lde = (1 + M) * F_
     nact, g1act = new(N, 4 * F_), new(N, F_)       # activated copies (scratch, shared by all layers)
-    eq_fused, eq_arith = eqff_fused_ok(cfg, N), (1 if proj.mode == "split" else 2)
-    if not save:                                   # inference: ping-pong work buffers, reused by every layer
-        h2, X2, t2 = new(N, F_), new(N, D, F_), new(E, F_)
-        nproj, xs, vs = new(N, 4 * F_), new(N, M * F_), new(N, M * F_)
-        eproj, attn = new(E, lde), new(E, H)
-        EQ, EK, Xp, w = new(N, D, Fe), new(N, D, Fe), new(N, D, F_), new(E, Fe)
-        ctx, pre_g1, mm = new(N, 2 * F_), new(N, F_), new(N, 2 * F_)
+    eq_fused = eqff_fused_ok(cfg, N)
+    if not save:                                   # inference: one set of work buffers, reused by every layer
+        lt, h2, X2, t2 = _layer_buffers(cfg, N, E, new, last=False, save=False)
 
     for li, lw in enumerate(pw.layers):
-        last = lw.Wt is None
+        first = zero_X_in(cfg, li)                  # X is the zero tensor made above; the tape carries the decision
         h_raw, X_raw = h, X
         if cfg.layernorm:                          # gotennet.py:397-398: the layer (and its residuals) see the normalised values
-            h = _norm_h(cfg, pw, lw, h)
+            h = _norm_h(lw, h, pw.emb_idx)
         if cfg.steerable_norm:
-            X = _norm_X(cfg, pw, lw, X)
+            X = _norm_X(lw, X, cfg.lmax, pw.emb_idx)
         if save:                                   # every layer keeps its own activations
-            lt = LayerTape(h_in=h, X_in=X, t_in=t, h_raw=h_raw, X_raw=X_raw)
+            lt, h2, X2, t2 = _layer_buffers(cfg, N, E, new, lw.Wt is None, True, pgrads)
+            lt.h_in, lt.t_in, lt.h_raw = h, t, h_raw
+            if not first:                          # (the uninitialised X of a zero-X_in layer never enters the tape)
+                lt.X_in, lt.X_raw = X, X_raw
             tape.layers.append(lt)
-            h2, X2 = new(N, F_), new(N, D, F_)
-            t2 = None if last else new(E, F_)
-            nproj, xs, vs = new(N, 4 * F_), new(N, M * F_), new(N, M * F_)
-            eproj, attn = new(E, lde), new(E, H)
-            Xp, ctx, pre_g1, mm = new(N, D, F_), new(N, 2 * F_), new(N, F_), new(N, 2 * F_)
-            if not last:
-                EQ, EK, w = new(N, D, Fe), new(N, D, Fe), new(E, Fe)
-                lt.pre_t = new(E, F_)
-                lt.EQ, lt.EK, lt.w = EQ, EK, w
-                lt.w_raw = new(E, Fe) if (cfg.htr_mode >> 2) else None
-            lt.nproj, lt.xs, lt.vs, lt.eproj, lt.attn = nproj, xs, vs, eproj, attn
-            lt.Xp, lt.ctx, lt.pre_g1, lt.mm = Xp, ctx, pre_g1, mm
-            if pgrads:                             # activated copies: one per layer instead of the shared scratch
-                nact, g1act = new(N, 4 * F_), new(N, F_)
-                lt.nact, lt.g1act = nact, g1act
-        # ---- GATA projections (gotennet.py:400-407).  The atom-sized node projection rides in the edge projection's
-        # launch (its 168 tiles fill the tail of the 5100-tile grid).  SiLU of the two hidden blocks is applied ONCE by
-        # the epilogue (a SiLU prologue in the two products below would redo it for each of their 4M column tiles); the
-        # pre-activation copy is what the backward needs.
-        first = zero_X_in(cfg, li)                  # X is the zero tensor made above: no tensor-gate blocks
-        We, be, ne = _We_first(cfg, lw) if first else (lw.We, lw.be, lde)
-        gemm_group([dict(A=t, lda=F_, W=We, bias=be, C=eproj, ldc=lde, rows=E, nout=ne, K=F_),
-                    dict(A=h, lda=F_, W=lw.Wn1, bias=lw.bn1, C=nact, ldc=4 * F_, rows=N, nout=4 * F_, K=F_,
-                         act=(2 * F_, 4 * F_), pre_out=nproj if save else None)])
-        nv = _value_first(cfg, lw) if first else M * F_
-        gemm_group([dict(A=nact, lda=4 * F_, W=lw.Ws20 if first else lw.Ws2, bias=lw.bs2, C=xs, ldc=M * F_, rows=N, nout=nv,
-                         K=F_, a_off=2 * F_),
-                    dict(A=nact, lda=4 * F_, W=lw.Wv20 if first else lw.Wv2, bias=lw.bv2, C=vs, ldc=M * F_, rows=N, nout=nv,
-                         K=F_, a_off=3 * F_)])
-        # ---- message / softmax / aggregate / residual (452-559, 613-640, 426-427)
-        message_stage(cfg, g, nact, xs, vs, eproj, attn, h, None if first else X, h2, X2)
+            if pgrads:
+                nact, g1act = lt.nact, lt.g1act
+        lt.first = first
+        _gata_forward(p, lw, lt, nact, h, X, t, h2, X2)
         h, h2 = h2, h
         X, X2 = X2, X
         if pgrads:
             lt.X_msg = X.clone()
-        # every product of the updated X (X W_vu^T for EQFF; EQ and the per-degree EK_l for HTR) in one launch
-        xprods = [dict(A=X, lda=F_, W=lw.Wvu, C=Xp, ldc=F_, rows=N * D, nout=F_, K=F_)]
-        if not last:
-            xprods.append(dict(A=X, lda=F_, W=lw.Wvq, C=EQ, ldc=Fe, rows=N * D, nout=Fe, K=F_))
-            if cfg.htr_mode & 1:                   # sep_htr=False: one W_vk for every row
-                xprods.append(dict(A=X, lda=F_, W=lw.Wvk[0], C=EK, ldc=Fe, rows=N * D, nout=Fe, K=F_))
-            else:
-                off = 0
-                for l in range(1, lmax + 1):
-                    cnt = 2 * l + 1
-                    xprods.append(dict(A=X, lda=F_, W=lw.Wvk[l - 1], C=EK, ldc=Fe, rows=N * cnt, nout=Fe, K=F_,
-                                       rowmap=(cnt, D, off)))
-                    off += cnt
-        gemm_group(xprods)
-        # ---- EQFF (731-746) and HTR edge weights (561-611).  Where covered the EQFF chain after X_p is ONE kernel
-        # (context, both gamma_m layers, update); else: context kernel, the first gamma_m layer riding in the launch of the
-        # edge-sized gamma_t product, the second layer, update kernel
-        m0 = None
-        if eq_fused:
-            call("gn_eqff_fused_forward", ptr(Xp), ptr(split_weight(lw.Wm0, proj.mode)), ptr(lw.bm0),
-                 ptr(split_weight(lw.Wm1, proj.mode)), ptr(lw.bm1), float(cfg.eps), N, F_, D, ptr(h), ptr(X),
-                 ptr(ctx) if save else None, ptr(pre_g1) if save else None, ptr(mm) if save else None, eq_arith, _stream())
-        else:
-            call("gn_eqff_context", ptr(h), ptr(Xp), float(cfg.eps), N, F_, D, ptr(ctx), _stream())
-            m0 = dict(A=ctx, lda=2 * F_, W=lw.Wm0, bias=lw.bm0, C=g1act, ldc=F_, rows=N, nout=F_, K=2 * F_, act=(0, F_),
-                      pre_out=pre_g1 if save else None)
-        if not last:
-            call("gn_htr_edge", ptr(EQ), ptr(EK), ptr(g.rl), ptr(g.rowptr), ptr(g.src), N, Fe, cfg.lmax_arg, cfg.htr_mode,
-                 ptr(lt.w_raw) if save else None, ptr(w), _stream())
-            if cfg.composed_update:
-                upd = _edge_update_composed(cfg, lw, t, w, t2, E, lt.pre_t if save else None)
-                if save:
-                    lt.upd = upd
-                gemm_group([m0])
-            else:
-                gemm_group([dict(A=t, lda=F_, W=lw.Wt, bias=lw.bt, C=t2, ldc=F_, rows=E, nout=F_, K=F_, act=(0, F_), res=t,
-                                 gate=w, pre_out=lt.pre_t if save else None), m0])
+        _eqff_htr_forward(p, lw, lt, g1act, h, X, t, t2, save, eq_fused)
+        if lw.Wt is not None:
             t, t2 = t2, t
-        else:
-            gemm_group([m0])
-        if not eq_fused:
-            gemm(g1act, F_, lw.Wm1, lw.bm1, mm, 2 * F_, N, 2 * F_, F_)
-            call("gn_eqff_update", ptr(mm), ptr(Xp), N, F_, D, ptr(h), ptr(X), _stream())
         if trace is not None:
             trace.append((h.clone(), X.clone(), t.clone()) if pw.emb_idx is None else
                          tuple(v.index_select(v.dim() - 1, pw.emb_idx) for v in (h, X, t)))
@@ -586,127 +656,47 @@ def _forward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, s
     return h, X, tape
 
 
-def _norm_h(cfg: Config, pw: PackedWeights, lw: LayerWeights, h: torch.Tensor) -> torch.Tensor:
-    """nn.LayerNorm on h at the GATA input (gotennet.py:397).  Embedded model: over the real channels (embed.py)."""
-    N = h.shape[0]
-    if pw.emb_idx is None:
-        hn = torch.empty_like(h)
-        call("gn_layernorm", ptr(h), ptr(lw.ln_w), ptr(lw.ln_b), 1e-5, N, cfg.F, ptr(hn), _stream())
-        return hn
-    hc = h.index_select(1, pw.emb_idx)
-    yc = torch.empty_like(hc)
-    call("gn_layernorm", ptr(hc), ptr(lw.ln_w), ptr(lw.ln_b), 1e-5, N, cfg.F_model, ptr(yc), _stream())
-    return torch.zeros_like(h).index_copy_(1, pw.emb_idx, yc)
-
-
-def _norm_X(cfg: Config, pw: PackedWeights, lw: LayerWeights, X: torch.Tensor) -> torch.Tensor:
-    """TensorLayerNorm on X at the GATA input (gotennet.py:398, layers.py:1497-1563)."""
-    N = X.shape[0]
-    if pw.emb_idx is None:
-        Xn = torch.empty_like(X)
-        call("gn_tensor_norm", ptr(X), ptr(lw.tln_w), 1e-12, N, cfg.F, cfg.lmax, ptr(Xn), _stream())
-        return Xn
-    Xc = X.index_select(2, pw.emb_idx)
-    Yc = torch.empty_like(Xc)
-    call("gn_tensor_norm", ptr(Xc), ptr(lw.tln_w), 1e-12, N, cfg.F_model, cfg.lmax, ptr(Yc), _stream())
-    return torch.zeros_like(X).index_copy_(2, pw.emb_idx, Yc)
-
-
-def gata_input_norms(cfg: Config, lw: LayerWeights, h: torch.Tensor, X: torch.Tensor):
-    """The optional input norms of a GATA layer (gotennet.py:397-398) on their own: -> (h or LN(h), X or TLN(X))."""
-    N, F_ = h.shape[0], cfg.F
-    if cfg.layernorm and N:
-        hn = torch.empty_like(h)
-        call("gn_layernorm", ptr(h), ptr(lw.ln_w), ptr(lw.ln_b), 1e-5, N, F_, ptr(hn), _stream())
-        h = hn
-    if cfg.steerable_norm and N:
-        Xn = torch.empty_like(X)
-        call("gn_tensor_norm", ptr(X), ptr(lw.tln_w), 1e-12, N, F_, cfg.lmax, ptr(Xn), _stream())
-        X = Xn
-    return h, X
-
-
-def _gata_layer_impl(cfg: Config, lw: LayerWeights, g: "Graph", h: torch.Tensor, X: torch.Tensor, t: torch.Tensor):
+def gata_layer(cfg: Config, lw: LayerWeights, g: "Graph", h: torch.Tensor, X: torch.Tensor, t: torch.Tensor):
     """ONE GATA layer (gotennet.py:366-450) on its own, inference only: what ``GATA.forward`` of the mirror module runs
     when a caller composes layers directly.  Same kernels as ``forward`` (which additionally fuses the neighbouring EQFF
     launches into the grouped GEMMs).  ``g`` carries the CSR view, rl and the cosine cutoff.  -> (h', X', t')."""
-    F_, H, D, M, lmax, Fe = cfg.F, cfg.H, cfg.D, cfg.M, cfg.lmax, cfg.Fe
-    N, E = g.N, g.E
-    proj = _Proj(cfg)
-    gemm, gemm_group = proj.gemm, proj.group
+    F_, D, M, Fe, N, E = cfg.F, cfg.D, cfg.M, cfg.Fe, g.N, g.E
+    p = _Call(cfg, g)
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=h.device)
-    last = lw.Wt is None
     if cfg.layernorm:
-        hn = new(N, F_)
-        call("gn_layernorm", ptr(h), ptr(lw.ln_w), ptr(lw.ln_b), 1e-5, N, F_, ptr(hn), _stream())
-        h = hn
+        h = _norm_h(lw, h)
     if cfg.steerable_norm:
-        Xn = new(N, D, F_)
-        call("gn_tensor_norm", ptr(X), ptr(lw.tln_w), 1e-12, N, F_, lmax, ptr(Xn), _stream())
-        X = Xn
-    lde = (1 + M) * F_
-    nact, xs, vs = new(N, 4 * F_), new(N, M * F_), new(N, M * F_)
-    eproj, attn = new(E, lde), new(E, H)
+        X = _norm_X(lw, X, cfg.lmax)
+    lt = LayerTape(xs=new(N, M * F_), vs=new(N, M * F_), eproj=new(E, p.lde), attn=new(E, cfg.H))
     h2, X2 = new(N, F_), new(N, D, F_)
-    gemm_group([dict(A=t, lda=F_, W=lw.We, bias=lw.be, C=eproj, ldc=lde, rows=E, nout=lde, K=F_),
-                dict(A=h, lda=F_, W=lw.Wn1, bias=lw.bn1, C=nact, ldc=4 * F_, rows=N, nout=4 * F_, K=F_,
-                     act=(2 * F_, 4 * F_))])
-    gemm_group([dict(A=nact, lda=4 * F_, W=lw.Ws2, bias=lw.bs2, C=xs, ldc=M * F_, rows=N, nout=M * F_, K=F_, a_off=2 * F_),
-                dict(A=nact, lda=4 * F_, W=lw.Wv2, bias=lw.bv2, C=vs, ldc=M * F_, rows=N, nout=M * F_, K=F_, a_off=3 * F_)])
-    message_stage(cfg, g, nact, xs, vs, eproj, attn, h, X, h2, X2)
-    h, X = h2, X2
-    if last:
-        return h, X, t
+    _gata_forward(p, lw, lt, new(N, 4 * F_), h, X, t, h2, X2)
+    if lw.Wt is None:
+        return h2, X2, t
     EQ, EK, w, t2 = new(N, D, Fe), new(N, D, Fe), new(E, Fe), new(E, F_)
-    xprods = [dict(A=X, lda=F_, W=lw.Wvq, C=EQ, ldc=Fe, rows=N * D, nout=Fe, K=F_)]
-    if cfg.htr_mode & 1:
-        xprods.append(dict(A=X, lda=F_, W=lw.Wvk[0], C=EK, ldc=Fe, rows=N * D, nout=Fe, K=F_))
-    else:
-        off = 0
-        for l in range(1, lmax + 1):
-            cnt = 2 * l + 1
-            xprods.append(dict(A=X, lda=F_, W=lw.Wvk[l - 1], C=EK, ldc=Fe, rows=N * cnt, nout=Fe, K=F_,
-                               rowmap=(cnt, D, off)))
-            off += cnt
-    gemm_group(xprods)
+    p.group(_htr_problems(p, lw, X2, EQ, EK))
     call("gn_htr_edge", ptr(EQ), ptr(EK), ptr(g.rl), ptr(g.rowptr), ptr(g.src), N, Fe, cfg.lmax_arg, cfg.htr_mode, None, ptr(w),
-         _stream())
+         p.st)
     if cfg.composed_update:
         _edge_update_composed(cfg, lw, t, w, t2, E, None)
     else:
-        gemm(t, F_, lw.Wt, lw.bt, t2, F_, E, F_, F_, act=(0, F_), res=t, gate=w)
-    return h, X, t2
+        p.gemm(t, F_, lw.Wt, lw.bt, t2, F_, E, F_, F_, act=(0, F_), res=t, gate=w)
+    return h2, X2, t2
 
 
-def _eqff_layer_impl(cfg: Config, lw: LayerWeights, h: torch.Tensor, X: torch.Tensor):
+def eqff_layer(cfg: Config, lw: LayerWeights, h: torch.Tensor, X: torch.Tensor):
     """ONE EQFF block (gotennet.py:716-748) on its own, inference only (``EQFF.forward`` of the mirror module).
     Returns NEW tensors (h', X')."""
-    F_, D = cfg.F, cfg.D
-    N = h.shape[0]
-    gemm = _Proj(cfg).gemm
+    F_, D, N = cfg.F, cfg.D, h.shape[0]
+    p = _Call(cfg)
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=h.device)
     Xp, ctx, g1, mm = new(N, D, F_), new(N, 2 * F_), new(N, F_), new(N, 2 * F_)
-    gemm(X, F_, lw.Wvu, None, Xp, F_, N * D, F_, F_)
-    call("gn_eqff_context", ptr(h), ptr(Xp), float(cfg.eps), N, F_, D, ptr(ctx), _stream())
-    gemm(ctx, 2 * F_, lw.Wm0, lw.bm0, g1, F_, N, F_, 2 * F_, act=(0, F_))
-    gemm(g1, F_, lw.Wm1, lw.bm1, mm, 2 * F_, N, 2 * F_, F_)
+    p.gemm(X, F_, lw.Wvu, None, Xp, F_, N * D, F_, F_)
+    call("gn_eqff_context", ptr(h), ptr(Xp), float(cfg.eps), N, F_, D, ptr(ctx), p.st)
+    p.gemm(ctx, 2 * F_, lw.Wm0, lw.bm0, g1, F_, N, F_, 2 * F_, act=(0, F_))
+    p.gemm(g1, F_, lw.Wm1, lw.bm1, mm, 2 * F_, N, 2 * F_, F_)
     h, X = h.clone(), X.clone()
-    call("gn_eqff_update", ptr(mm), ptr(Xp), N, F_, D, ptr(h), ptr(X), _stream())
+    call("gn_eqff_update", ptr(mm), ptr(Xp), N, F_, D, ptr(h), ptr(X), p.st)
     return h, X
-
-
-def message_stage(cfg: Config, g: "Graph", nact, xs, vs, eproj, attn, h, X, h2, X2):
-    """GATA message stage (gotennet.py:452-559, 613-640, 426-427): scores + segment softmax, message, aggregate,
-    residual.  q | k are columns [0, 2F) of ``nact``; t_attn (pre-activation) columns [0, F) of ``eproj``, t_filter the
-    rest."""
-    F_, H, M = cfg.F, cfg.H, cfg.M
-    lde = (1 + M) * F_
-    call("gn_attn_softmax", ptr(nact), nact.data_ptr() + 4 * F_, 4 * F_, ptr(eproj), lde,
-         ptr(g.rowptr), ptr(g.src), ptr(g.outdeg), g.N, F_, H, ptr(attn), cfg.act, _stream())
-    call("gn_message_aggregate", ptr(xs), ptr(vs), M * F_, eproj.data_ptr() + 4 * F_, lde,
-         ptr(attn), ptr(g.rl), ptr(g.cut), ptr(g.rowptr), ptr(g.src),
-         ptr(h), ptr(X), ptr(h2), ptr(X2), g.N, F_, H, cfg.lmax_arg_msg, int(cfg.sep_dir), int(cfg.sep_tensor), _stream())
-
 
 #: ``fuse_eqff = None`` (auto): fused up to this many atoms per call (measured crossover between 672 and 2688 atoms at F = 256)
 EQFF_FUSED_MAX_ATOMS = 1024
@@ -728,7 +718,7 @@ def _edge_update_composed(cfg: Config, lw: LayerWeights, t, w_raw, t2, E: int, p
     gamma_t = Dense -> [LayerNorm edge_ln] -> SiLU -> Dense [-> SiLU unless "mlp"]  ("mlp"/"mlpa"), or the
     default SiLU(Dense).  Returns the intermediates the backward needs."""
     F_, Fe, Fm = cfg.F, cfg.Fe, cfg.Fm
-    gemm = _Proj(cfg).gemm
+    gemm = _Call(cfg).gemm
     new = lambda width=F_: torch.empty((E, width), dtype=torch.float32, device=t.device)
     st = _stream()
     u = dict(w_raw=w_raw)
@@ -770,7 +760,7 @@ def _edge_update_composed(cfg: Config, lw: LayerWeights, t, w_raw, t2, E: int, p
 def _edge_update_composed_backward(cfg: Config, lw: LayerWeights, lt, gt, gt_a, E: int):
     """Input-gradients of _edge_update_composed: writes gt_a = gt + (d/dt through gamma_t) and returns dL/dw [E,F]."""
     F_, Fe, Fm = cfg.F, cfg.Fe, cfg.Fm
-    gemm = _Proj(cfg).gemm
+    gemm = _Call(cfg).gemm
     new = lambda width=F_: torch.empty((E, width), dtype=torch.float32, device=gt.device)
     st = _stream()
     u = lt.upd
@@ -853,7 +843,220 @@ def empty_grads(pw: PackedWeights) -> PackedWeights:
     return out
 
 
-def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, tape: Tape,
+def _partial_sum_layout(cfg: Config, pw: PackedWeights) -> dict:
+    """The slices of the per-edge partial sums dL/drl [n_rl, E, D] and dL/dcut [n_cut, E]: every contributing kernel writes
+    its own and gn_edge_geometry_backward adds them in index order, so the slice numbers are part of the bits:
+      rl:   Wm per message backward (layer li: from ``msg_rl * li``), then Wh per HTR backward in layer order (``htr_rl[li]``);
+      cut:  Wm * G per message backward (G degree groups; from ``msg_cut * li``), then Wm of the node-init backward (``init_cut``).
+    Wm, Wh: partial slices per writing call (a slot wider than a wave writes one per 64-lane part: F / 256, Fe / 256)."""
+    L = len(pw.layers)
+    G = _lib.load().gn_message_backward_groups(cfg.lmax_arg_msg_bwd, int(cfg.sep_dir), int(cfg.sep_tensor), cfg.act)
+    Wm, Wh = max(1, cfg.F // 256), max(1, cfg.Fe // 256)
+    htr = [li for li, lw in enumerate(pw.layers) if lw.Wt is not None]
+    return dict(G=G, msg_rl=Wm, msg_cut=Wm * G, init_cut=Wm * G * L, htr_rl={li: Wm * L + Wh * i for i, li in enumerate(htr)},
+                n_rl=Wm * L + Wh * len(htr), n_cut=Wm * (G * L + 1))
+
+
+@dataclass
+class _BackwardWork:
+    """Work buffers of ``backward``, reused by every layer, with the slice layout of the partial sums and the by-source
+    view of the graph: made by ``_backward_work``, which says what each buffer holds."""
+    gh: Any; gX: Any; gt: Any; colptr: Any; perm: Any; g_rl_parts: Any; g_cut_parts: Any; ga_parts: Any
+    G: int; msg_rl: int; msg_cut: int; init_cut: int; htr_rl: dict; n_rl: int; n_cut: int
+    gm: Any; gXp: Any; g_g1: Any; g_ctx: Any; gh1: Any; gX1: Any; gh2: Any; gX2: Any; gh_qk: Any; gEQ: Any; gEK: Any
+    g_eproj: Any; g_s: Any; g_nproj: Any; g_x: Any; g_v: Any; gt_a: Any; gt_b: Any; g_pre_t: Any
+
+
+def _backward_work(cfg: Config, pw: PackedWeights, g: Graph, f32: dict, gh, gX, eq_fused: bool) -> _BackwardWork:
+    """The caller's adjoints brought into the engine's layout, and every work buffer (the ONE allocation site)."""
+    F_, D, M, H, Fe, N, E = cfg.F, cfg.D, cfg.M, cfg.H, cfg.Fe, g.N, g.E
+    new = lambda *shape: torch.empty(shape, **f32)
+    if pw.emb_idx is not None:                     # embedded model: gradients arrive in the real layout
+        gh = torch.zeros((N, F_), **f32).index_copy_(1, pw.emb_idx, gh.contiguous())
+        if gX is not None:
+            gX = torch.zeros((N, D, F_), **f32).index_copy_(2, pw.emb_idx, gX.contiguous())
+    # dL/dX = None (an energy head reads h only): the un-fused EQFF backward takes a null pointer for it (no zero-filled
+    # [N,D,F] tensor is made, written or read); the fused kernel wants the tensor
+    if gX is None and eq_fused:
+        gX = torch.zeros((N, D, F_), **f32)
+    lay = _partial_sum_layout(cfg, pw)
+    colptr, perm = g.csc()
+    return _BackwardWork(
+        # dL/d of the current layer's output h, X (None = 0), t (None = 0: nothing above the last layer reads t): rotate per layer
+        gh=gh.contiguous(), gX=None if gX is None else gX.contiguous(), gt=None, colptr=colptr, perm=perm, **lay,
+        g_rl_parts=new(lay["n_rl"], E, D), g_cut_parts=new(lay["n_cut"], E),
+        # head sums of g_a: G partial slices (degree groups), or the merged kernel's one; aggr = "max": the per-message
+        # gradient workspace of the routing kernel instead
+        ga_parts=new(E, 1 + D, F_) if cfg.aggr == 2 else new(lay["G"], E, H),
+        gm=new(N, 2 * F_), gXp=new(N, D, F_), g_g1=new(N, F_), g_ctx=new(N, 2 * F_),     # EQFF: dL/d mm, X_p, pre_g1, context
+        gh1=new(N, F_), gX1=new(N, D, F_),             # dL/d of the message stage's output
+        gh2=new(N, F_), gX2=new(N, D, F_), gh_qk=new(N, F_),     # dL/d of the layer's input (gh_qk: its q | k part)
+        gEQ=new(N, D, Fe), gEK=new(N, D, Fe),          # HTR
+        g_eproj=new(E, (1 + M) * F_), g_s=new(E, H), g_nproj=new(N, 4 * F_), g_x=new(N, M * F_), g_v=new(N, M * F_),   # message backward
+        gt_a=new(E, F_), gt_b=new(E, F_), g_pre_t=new(E, F_))   # dL/dt after the edge update / of the layer input; dL/d pre_t
+
+
+def _eqff_htr_backward(p: _Call, lw: LayerWeights, lt: LayerTape, wb: _BackwardWork, li: int, eq_fused: bool, gw):
+    """EQFF backward (reads gh, gX: writes gXp, gh1 -- and gm, g_g1, g_ctx un-fused); independent of it, the HTR + edge-update
+    backward of a layer that has one (reads gt: writes gEQ, gEK, g_pre_t, gt_a, the layer's HTR slice of dL/drl); then the
+    X-products' (gX1 = dL/dX at the message stage's output).  ``gw``: the layer's parameter-gradient storage or None.
+    -> dL/dt at the layer's message stage (gt_a, or gt itself where t passes through unchanged)."""
+    cfg, g, st, F_, D, Fe, N, E = p.cfg, p.g, p.st, p.F, p.D, p.Fe, p.N, p.E
+    gh, gX, gt = wb.gh, wb.gX, wb.gt
+    m1 = None
+    if eq_fused:                                   # one kernel
+        call("gn_eqff_fused_backward", ptr(gh), ptr(gX), ptr(lt.mm), ptr(lt.Xp), ptr(lt.ctx), ptr(lt.pre_g1),
+             ptr(split_weight(_T(lw, "Wm1"), p.mode)), ptr(split_weight(_T(lw, "Wm0"), p.mode)), N, F_, D,
+             ptr(wb.gXp), ptr(wb.gh1), 1 if p.mode == "split" else 2, st)
+    else:                                          # its first half here; the gamma_m.1 product rides below
+        call("gn_eqff_backward_a", ptr(gh), ptr(gX), ptr(lt.mm), ptr(lt.Xp), N, F_, D, ptr(wb.gm), ptr(wb.gXp), st)
+        m1 = dict(A=wb.gm, lda=2 * F_, W=_T(lw, "Wm1"), C=wb.g_g1, ldc=F_, rows=N, nout=F_, K=2 * F_,
+                  dgate=lt.pre_g1)                 # * SiLU'(pre) in the epilogue
+    if lw.Wt is None:
+        p.group([m1])
+        gt_in = gt                                 # no edge update in this layer: t passes through unchanged
+    else:
+        if gt is None:
+            raise RuntimeError("internal: missing edge gradient")
+        rl_slice = wb.g_rl_parts.data_ptr() + 4 * E * D * wb.htr_rl[li]
+        if cfg.composed_update:                    # gt_a = gt + gamma_t backward; g_w = gamma_w backward
+            g_w = _edge_update_composed_backward(cfg, lw, lt, gt, wb.gt_a, E)
+            call("gn_htr_backward", ptr(g_w), None, None, None, ptr(lt.EQ), ptr(lt.EK), ptr(g.rl),
+                 ptr(g.rowptr), ptr(g.src), ptr(g.tgt_by_src), ptr(wb.colptr), ptr(wb.perm), N, Fe, cfg.lmax_arg_bwd, cfg.htr_mode | 16,
+                 ptr(wb.gEQ), ptr(wb.gEK), rl_slice, None, cfg.act, st)
+            p.group([m1])
+        else:
+            call("gn_htr_backward", ptr(gt), ptr(lt.pre_t), ptr(lt.w), ptr(lt.w_raw), ptr(lt.EQ), ptr(lt.EK),
+                 ptr(g.rl), ptr(g.rowptr), ptr(g.src), ptr(g.tgt_by_src), ptr(wb.colptr), ptr(wb.perm), N, Fe, cfg.lmax_arg_bwd,
+                 cfg.htr_mode, ptr(wb.gEQ), ptr(wb.gEK), rl_slice, ptr(wb.g_pre_t), cfg.act, st)
+            # gt_a = gt + ((gt * w) * SiLU'(pre_t)) Wt; the atom-sized gamma_m product rides in its launch
+            p.group([dict(A=wb.g_pre_t, lda=F_, W=_T(lw, "Wt"), C=wb.gt_a, ldc=F_, rows=E, nout=F_, K=F_, res=gt), m1])
+        gt_in = wb.gt_a
+    if not eq_fused:                               # EQFF backward, second half
+        p.gemm(wb.g_g1, F_, _T(lw, "Wm0"), None, wb.g_ctx, 2 * F_, N, 2 * F_, F_)
+        call("gn_eqff_backward_b", ptr(wb.g_ctx), ptr(lt.ctx), ptr(lt.Xp), ptr(gh), N, F_, D, ptr(wb.gXp), ptr(wb.gh1), st)
+    if gw is not None:
+        _layer_weight_grads_eqff_htr(cfg, gw, lt, wb, N, E)
+    # ---- gX1 = gX + gXp W_vu (+ gEQ W_vq + gEK_l W_vk_l)
+    gX1, gXp = wb.gX1, wb.gXp
+    if lw.Wt is None:
+        p.gemm(gXp, F_, _T(lw, "Wvu"), None, gX1, F_, N * D, F_, F_, res=gX)
+    elif Fe == F_:
+        # one launch; per degree block: A = [gXp | gEQ | gEK] (K-segmented), W = [W_vu^T | W_vq^T | W_vk_l^T] along K
+        wcat = lambda k: derived(lw, ("Xcat", k), lambda: torch.cat([_T(lw, "Wvu"), _T(lw, "Wvq"), lw.Wvk[k].t()], 1).contiguous())
+        p.group([dict(A=gXp, A2=wb.gEQ, A3=wb.gEK, a_seg=F_, lda=F_, W=wcat(k), C=gX1, ldc=F_, rows=rows,
+                      nout=F_, K=3 * F_, rowmap=rowmap, res=gX) for k, rows, rowmap in p.blocks])
+    else:                                          # evec_dim != F: three chained products
+        p.gemm(gXp, F_, _T(lw, "Wvu"), None, gX1, F_, N * D, F_, F_, res=gX)
+        p.gemm(wb.gEQ, Fe, _T(lw, "Wvq"), None, gX1, F_, N * D, F_, Fe, res=gX1)
+        for k, rows, rowmap in p.blocks:
+            wkT = derived(lw, ("Wvk", k), lambda: lw.Wvk[k].t().contiguous())
+            p.gemm(wb.gEK, Fe, wkT, None, gX1, F_, rows, F_, Fe, rowmap=rowmap, res=gX1)
+    return gt_in
+
+
+def _layer_weight_grads_eqff_htr(cfg: Config, gw: LayerWeights, lt: LayerTape, wb: _BackwardWork, N: int, E: int):
+    """dL/d of gamma_m, W_vu and -- in a layer with an edge update -- gamma_t, W_vq, W_vk.  Reads gm, g_g1, gXp, g_pre_t,
+    gEQ, gEK, which the next layer's ``_eqff_htr_backward`` overwrites: called as soon as this layer's has written them."""
+    F_, D, Fe = cfg.F, cfg.D, cfg.Fe
+    probs = [dict(dY=wb.gm, ldy=2 * F_, A=lt.g1act, lda=F_, dW=gw.Wm1, db=gw.bm1, rows=N, nout=2 * F_, K=F_),
+             dict(dY=wb.g_g1, ldy=F_, A=lt.ctx, lda=2 * F_, dW=gw.Wm0, db=gw.bm0, rows=N, nout=F_, K=2 * F_),
+             dict(dY=wb.gXp, ldy=F_, A=lt.X_msg, lda=F_, dW=gw.Wvu, rows=N * D, nout=F_, K=F_)]
+    if gw.Wt is not None:
+        probs += [dict(dY=wb.g_pre_t, ldy=F_, A=lt.t_in, lda=F_, dW=gw.Wt, db=gw.bt, rows=E, nout=F_, K=F_),
+                  dict(dY=wb.gEQ, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvq, rows=N * D, nout=Fe, K=F_)]
+        probs += [dict(dY=wb.gEK, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvk[k], rows=rows, nout=Fe, K=F_, rowmap=rowmap)
+                  for k, rows, rowmap in cfg.degree_blocks(N)]
+    weight_grad_group(probs)
+
+
+def _gata_backward(p: _Call, lw: LayerWeights, lt: LayerTape, wb: _BackwardWork, li: int, gt_in, gw):
+    """Message backward and the GATA projections' input-gradients: reads gh1, gX1 and ``gt_in`` (dL/dt at the message
+    stage), writes gh2, gX2 (not for a zero-X_in layer), gt_b = dL/d of the layer's (normalised) input h, X, t and the
+    final g_eproj, g_nproj, g_x, g_v.  ``gw``: the layer's parameter-gradient storage or None."""
+    cfg, g, F_, D, lde, N, E, first, G = p.cfg, p.g, p.F, p.D, p.lde, p.N, p.E, lt.first, wb.G
+    H, M = cfg.H, cfg.M
+    if not first and lt.X_in is None:
+        raise RuntimeError("internal: the tape of a general-path layer holds no X_in")
+    if first and G > 1:                            # one launch instead of G degree groups: one g_cut slice is written
+        wb.g_cut_parts[wb.msg_cut * li + 1:wb.msg_cut * li + G].zero_()   # (never with wide slots: zero_X_in excludes them)
+    call("gn_message_backward", ptr(lt.xs), ptr(lt.vs), M * F_, ptr(lt.eproj), lde, ptr(lt.attn),
+         ptr(lt.nproj), 4 * F_, None if first else ptr(lt.X_in), ptr(g.rl), ptr(g.cut), ptr(g.outdeg),
+         ptr(wb.gh1), ptr(wb.gX1), ptr(g.rowptr), ptr(g.src), ptr(g.tgt_by_src), ptr(wb.colptr), ptr(wb.perm),
+         ptr(wb.g_eproj), ptr(wb.g_s), ptr(wb.g_nproj), 4 * F_, ptr(wb.g_x), ptr(wb.g_v), None if first else ptr(wb.gX2),
+         wb.g_rl_parts.data_ptr() + 4 * E * D * wb.msg_rl * li, wb.g_cut_parts.data_ptr() + 4 * E * wb.msg_cut * li,
+         None if (MSG_BWD_PAIR and (first or G == 1)) else ptr(wb.ga_parts), E,
+         N, F_, H, cfg.lmax_arg_msg_bwd, int(cfg.sep_dir), int(cfg.sep_tensor), cfg.act, p.st)
+    # the edge-sized W_e^T product leaves 0.7 of its last tile round idle: the two K-heavy atom-sized products
+    # (g_x W_s2, g_v W_v2; 60 us as a launch of their own) ride there; W_n1^T needs their output and follows alone.
+    # A zero-X_in layer: the tensor-gate columns of g_eproj, g_x, g_v were not written -- K-prefixes
+    ke, kv = p.cols[first]
+    g_nproj = wb.g_nproj
+    p.group([dict(A=wb.g_eproj, lda=lde, W=_T(lw, "We", 0, ke), C=wb.gt_b, ldc=F_, rows=E, nout=F_, K=ke, res=gt_in),
+             dict(A=wb.g_x, lda=M * F_, W=_T(lw, "Ws2", 0, kv), C=g_nproj, ldc=4 * F_, rows=N, nout=F_, K=kv, c_off=2 * F_,
+                  dgate=lt.nproj, g_off=2 * F_),
+             dict(A=wb.g_v, lda=M * F_, W=_T(lw, "Wv2", 0, kv), C=g_nproj, ldc=4 * F_, rows=N, nout=F_, K=kv, c_off=3 * F_,
+                  dgate=lt.nproj, g_off=3 * F_),
+             # the q | k half of the W_n1^T product needs only the message backward's g_q | g_k: it rides here
+             # too and halves the K of the product that has to wait for the two riders above (33 -> 20 us)
+             dict(A=g_nproj, lda=4 * F_, W=_T(lw, "Wn1", 0, 2 * F_), C=wb.gh_qk, ldc=F_, rows=N, nout=F_, K=2 * F_, res=wb.gh1)])
+    p.gemm(g_nproj, 4 * F_, _T(lw, "Wn1", 2 * F_, 4 * F_), None, wb.gh2, F_, N, F_, 2 * F_, res=wb.gh_qk, a_off=2 * F_)
+    if gw is not None:
+        _layer_weight_grads_gata(p, gw, lt, wb)
+
+
+def _layer_weight_grads_gata(p: _Call, gw: LayerWeights, lt: LayerTape, wb: _BackwardWork):
+    """dL/d of the GATA projections [W_re; W_rs], W_n1, gamma_s.1, gamma_v.1.  Reads g_eproj, g_nproj, g_x, g_v, final
+    at the end of ``_gata_backward`` and overwritten by the next layer's: called there."""
+    F_, M, lde, N, E = p.F, p.cfg.M, p.lde, p.N, p.E
+    ne, nv = p.cols[lt.first]
+    weight_grad_group([
+        dict(dY=wb.g_eproj, ldy=lde, A=lt.t_in, lda=F_, dW=gw.We, db=gw.be, rows=E, nout=ne, K=F_),
+        dict(dY=wb.g_nproj, ldy=4 * F_, A=lt.h_in, lda=F_, dW=gw.Wn1, db=gw.bn1, rows=N, nout=4 * F_, K=F_),
+        dict(dY=wb.g_x, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=2 * F_, dW=gw.Ws2, db=gw.bs2, rows=N, nout=nv, K=F_),
+        dict(dY=wb.g_v, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=3 * F_, dW=gw.Wv2, db=gw.bv2, rows=N, nout=nv, K=F_)])
+    if lt.first:                                   # a zero-X_in layer: the tensor-gate rows get exactly zero
+        for t_, n in ((gw.We, ne), (gw.be, ne), (gw.Ws2, nv), (gw.bs2, nv), (gw.Wv2, nv), (gw.bv2, nv)):
+            t_[n:].zero_()
+
+
+def _init_backward(p: _Call, pw: PackedWeights, z32, tape: Tape, wb: _BackwardWork, new):
+    """EdgeInit / NodeInit backward (layers.py:1658-1714): reads gt, gh (adds the EdgeInit part to gh in place), writes
+    g_ctx and the node-init slice of dL/dcut.  -> (g_feat [E,2F], gy, gy1: dL/d of NodeInit's LayerNorm output and input)."""
+    cfg, g, st, F_, N, E = p.cfg, p.g, p.st, p.F, p.N, p.E
+    g_feat = new(E, 2 * F_)
+    call("gn_edge_init_backward", ptr(wb.gt), ptr(tape.h0), ptr(tape.feat), 2 * F_, ptr(g.rowptr), ptr(g.src),
+         ptr(wb.colptr), ptr(wb.perm), N, F_, ptr(g_feat), ptr(wb.gh), st)
+    Fc = cfg.Fc or F_
+    gy = new(N, Fc)
+    p.gemm(wb.gh, F_, _T(pw, "Wb"), None, gy, Fc, N, Fc, F_)
+    gy1 = new(N, Fc)
+    call("gn_layernorm_silu_backward", ptr(tape.y_pre), ptr(pw.ln_w), ptr(pw.ln_b), 1e-5, ptr(gy), N, Fc, ptr(gy1), cfg.act, st)
+    p.gemm(gy1, Fc, _T(pw, "Wa"), None, wb.g_ctx, 2 * F_, N, 2 * F_, Fc)
+    call("gn_node_init_backward", ptr(wb.g_ctx), ptr(z32), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(pw.A_nbr),
+         ptr(g.rowptr), ptr(g.src), N, F_, ptr(g_feat), wb.g_cut_parts.data_ptr() + 4 * E * wb.init_cut, st)
+    return g_feat, gy, gy1
+
+
+def _init_weight_grads(cfg, pw: PackedWeights, gw: PackedWeights, z32, g: Graph, tape: Tape, wb: _BackwardWork, g_feat, gy, gy1, new):
+    """dL/d of W_init, NodeInit's two layers and LayerNorm, and the embeddings A_na / A_nbr.  Reads gh, g_ctx and the
+    results of ``_init_backward`` (all final by then); nothing after it overwrites them, it just follows."""
+    F_, R, N, E, Fc = cfg.F, cfg.R, g.N, g.E, cfg.Fc or cfg.F
+    layernorm_param_grad(tape.y_pre, pw.ln_w, pw.ln_b, gy, cfg.act, gw.ln_w, gw.ln_b)
+    weight_grad_group([dict(dY=wb.gh, ldy=F_, A=tape.y, lda=Fc, dW=gw.Wb, db=gw.bb, rows=N, nout=F_, K=Fc),
+                       dict(dY=gy1, ldy=Fc, A=tape.ctx0, lda=2 * F_, dW=gw.Wa, db=gw.ba, rows=N, nout=Fc, K=2 * F_),
+                       dict(dY=g_feat, ldy=2 * F_, A=g.phi, lda=R, dW=gw.Winit, db=gw.binit, rows=E, nout=2 * F_, K=R)])
+    # species order of the atoms (integer plumbing): a stable argsort of z and the first sorted position of each species
+    n_sp = pw.A_na.shape[0]
+    zs, order = torch.sort(z32.long(), stable=True)
+    sp_ptr = torch.searchsorted(zs, torch.arange(n_sp + 1, device=zs.device)).to(torch.int32)
+    order = order.to(torch.int32)
+    per_src = new(N, F_)                           # per-source sums of the A_nbr gradient (named: alive until the launch)
+    call("gn_embedding_grad", ptr(wb.g_ctx), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(g.dst), ptr(wb.colptr), ptr(wb.perm),
+         ptr(order), ptr(sp_ptr), n_sp, N, F_, ptr(per_src), ptr(gw.A_na), ptr(gw.A_nbr), _stream())
+
+
+def backward(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, tape: Tape,
              gh: torch.Tensor, gX: Optional[torch.Tensor], trace: Optional[list] = None,
              pgrads: Optional[PackedWeights] = None, geometry: bool = True):
     """Input-gradients of ``forward``: given dL/dh [N,F] and dL/dX [N,D,F] (or None = 0)
@@ -873,11 +1076,8 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
             sel = lambda k, v: (v.clone() if pw.emb_idx is None or k in ("phi", "vec", "diff") else
                                 v.index_select(v.dim() - 1, pw.emb_idx))
             trace.append(dict(stage=stage, layer=li, **{k: None if v is None else sel(k, v) for k, v in ts.items()}))
-    F_, R, H, D, M, lmax = cfg.F, cfg.R, cfg.H, cfg.D, cfg.M, cfg.lmax
-    Fe = cfg.Fe
-    N, E = g.N, g.E
-    proj = _Proj(cfg)
-    gemm, gemm_group = proj.gemm, proj.group
+    F_, R, D, N, E = cfg.F, cfg.R, cfg.D, g.N, g.E
+    p = _Call(cfg, g, explicit_blocks=True)
     f32 = dict(dtype=torch.float32, device=z32.device)
     new = lambda *shape: torch.empty(shape, **f32)
     check_backward_supported(cfg)
@@ -885,251 +1085,54 @@ def _backward_impl(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, 
         check_param_grads_supported(cfg)
         if cfg.fuse_eqff is not False or tape.ctx0 is None:
             raise ValueError("internal: parameter gradients need the tape of a parameter-gradient forward")
-    colptr, perm = g.csc()
-    lde = (1 + M) * F_
-    eq_fused, eq_arith = eqff_fused_ok(cfg, N), (1 if proj.mode == "split" else 2)
-
-    # every contributing kernel writes its own slice; the geometry backward sums them in a fixed order
-    L = len(pw.layers)
-    G = _lib.load().gn_message_backward_groups(cfg.lmax_arg_msg_bwd, int(cfg.sep_dir), int(cfg.sep_tensor), cfg.act)
-    # W: partial slices per writing call (a slot wider than a wave writes one per 64-lane part: F / 256, Fe / 256 for HTR)
-    Wm, Wh = max(1, F_ // 256), max(1, Fe // 256)
-    n_htr = sum(lw.Wt is not None for lw in pw.layers)
-    n_rl, n_cut = Wm * L + Wh * n_htr, Wm * (G * L + 1)
-    g_rl_parts, g_cut_parts = new(n_rl, E, D), new(n_cut, E)
-    ga_parts = new(G, E, H)                        # head sums of g_a: G partial slices (degree groups), or the merged kernel's one
-    if cfg.aggr == 2:                              # aggr = "max": the per-message gradient workspace of the routing kernel
-        ga_parts = new(E, 1 + D, F_)
-    rl_slice = lambda q: g_rl_parts.data_ptr() + 4 * q * E * D
-    cut_slice = lambda q: g_cut_parts.data_ptr() + 4 * q * E
-    htr_slice = {}                                 # layer -> first g_rl slice of its HTR backward (after the message slices)
-    for li_, lw_ in enumerate(pw.layers):
-        if lw_.Wt is not None:
-            htr_slice[li_] = Wm * L + Wh * len(htr_slice)
-    if pw.emb_idx is not None:                     # embedded model: gradients arrive in the real layout
-        z_ = torch.zeros((N, F_), **f32)
-        gh = z_.index_copy_(1, pw.emb_idx, gh.contiguous())
-        if gX is not None:
-            gX = torch.zeros((N, D, F_), **f32).index_copy_(2, pw.emb_idx, gX.contiguous())
-    gh = gh.contiguous()
-    # dL/dX = None (an energy head reads h only): the un-fused EQFF backward takes a null pointer for it (no zero-filled
-    # [N,D,F] tensor is made, written or read); the fused kernel wants the tensor
-    if gX is None:
-        gX = torch.zeros((N, D, F_), **f32) if eq_fused else None
-    else:
-        gX = gX.contiguous()
-    gh_caller, gX_caller = gh, gX                  # read-only: never enter the work-buffer rotation below
-    gt = None                                      # dL/dt of the layer output (None = 0)
-
-    gm, gXp, g_g1, g_ctx = new(N, 2 * F_), new(N, D, F_), new(N, F_), new(N, 2 * F_)
-    gh1, gX1, gX2, gh2, gh_qk = new(N, F_), new(N, D, F_), new(N, D, F_), new(N, F_), new(N, F_)
-    gEQ, gEK = new(N, D, Fe), new(N, D, Fe)
-    g_eproj, g_s = new(E, lde), new(E, H)
-    g_nproj, g_x, g_v = new(N, 4 * F_), new(N, M * F_), new(N, M * F_)
-    gt_a, gt_b, g_pre_t = new(E, F_), new(E, F_), new(E, F_)
+    eq_fused = eqff_fused_ok(cfg, N)
+    wb = _backward_work(cfg, pw, g, f32, gh, gX, eq_fused)
+    gh_caller, gX_caller = wb.gh, wb.gX            # read-only: never enter the work-buffer rotation below
 
     for li in reversed(range(len(pw.layers))):
         lw, lt = pw.layers[li], tape.layers[li]
-        last = lw.Wt is None
-        first = zero_X_in(cfg, li)
+        gw = pgrads.layers[li] if pgrads is not None else None
         if snap is not None:
-            snap("layer", li, h=gh, X=gX if gX is not None else torch.zeros((N, D, F_), **f32),
-                 t=gt if gt is not None else torch.zeros((E, F_), **f32))
-        # ---- EQFF backward (one kernel where covered; else its first half here); HTR backward kernels (independent of it)
-        m1 = None
-        if eq_fused:
-            call("gn_eqff_fused_backward", ptr(gh), ptr(gX), ptr(lt.mm), ptr(lt.Xp), ptr(lt.ctx), ptr(lt.pre_g1),
-                 ptr(split_weight(_T(lw, "Wm1"), proj.mode)), ptr(split_weight(_T(lw, "Wm0"), proj.mode)), N, F_, D,
-                 ptr(gXp), ptr(gh1), eq_arith, _stream())
-        else:
-            call("gn_eqff_backward_a", ptr(gh), ptr(gX), ptr(lt.mm), ptr(lt.Xp), N, F_, D, ptr(gm), ptr(gXp), _stream())
-            m1 = dict(A=gm, lda=2 * F_, W=_T(lw, "Wm1"), C=g_g1, ldc=F_, rows=N, nout=F_, K=2 * F_,
-                      dgate=lt.pre_g1)             # * SiLU'(pre) in the epilogue
-        if not last:
-            if gt is None:
-                raise RuntimeError("internal: missing edge gradient")
-            if cfg.composed_update:                # gt_a = gt + gamma_t backward; g_w = gamma_w backward
-                g_w = _edge_update_composed_backward(cfg, lw, lt, gt, gt_a, E)
-                call("gn_htr_backward", ptr(g_w), None, None, None, ptr(lt.EQ), ptr(lt.EK), ptr(g.rl),
-                     ptr(g.rowptr), ptr(g.src), ptr(g.tgt_by_src), ptr(colptr), ptr(perm), N, Fe, cfg.lmax_arg_bwd, cfg.htr_mode | 16,
-                     ptr(gEQ), ptr(gEK), rl_slice(htr_slice[li]), None, cfg.act, _stream())
-                gemm_group([m1])
-            else:
-                call("gn_htr_backward", ptr(gt), ptr(lt.pre_t), ptr(lt.w), ptr(lt.w_raw), ptr(lt.EQ), ptr(lt.EK),
-                     ptr(g.rl), ptr(g.rowptr), ptr(g.src), ptr(g.tgt_by_src), ptr(colptr), ptr(perm), N, Fe, cfg.lmax_arg_bwd,
-                     cfg.htr_mode, ptr(gEQ), ptr(gEK), rl_slice(htr_slice[li]), ptr(g_pre_t), cfg.act, _stream())
-                # gt_a = gt + ((gt * w) * SiLU'(pre_t)) Wt; the atom-sized gamma_m product rides in its launch
-                gemm_group([dict(A=g_pre_t, lda=F_, W=_T(lw, "Wt"), C=gt_a, ldc=F_, rows=E, nout=F_, K=F_, res=gt), m1])
-            gt_in = gt_a
-        else:
-            gemm_group([m1])
-            gt_in = gt                             # no edge update in this layer: t passes through unchanged
-        # ---- EQFF backward, second half
-        if not eq_fused:
-            gemm(g_g1, F_, _T(lw, "Wm0"), None, g_ctx, 2 * F_, N, 2 * F_, F_)
-            call("gn_eqff_backward_b", ptr(g_ctx), ptr(lt.ctx), ptr(lt.Xp), ptr(gh), N, F_, D, ptr(gXp), ptr(gh1), _stream())
-        if pgrads is not None:                     # before the next layer's backward reuses gm, g_g1, gXp, g_pre_t, gEQ, gEK
-            gw = pgrads.layers[li]
-            probs = [dict(dY=gm, ldy=2 * F_, A=lt.g1act, lda=F_, dW=gw.Wm1, db=gw.bm1, rows=N, nout=2 * F_, K=F_),
-                     dict(dY=g_g1, ldy=F_, A=lt.ctx, lda=2 * F_, dW=gw.Wm0, db=gw.bm0, rows=N, nout=F_, K=2 * F_),
-                     dict(dY=gXp, ldy=F_, A=lt.X_msg, lda=F_, dW=gw.Wvu, rows=N * D, nout=F_, K=F_)]
-            if not last:
-                probs += [dict(dY=g_pre_t, ldy=F_, A=lt.t_in, lda=F_, dW=gw.Wt, db=gw.bt, rows=E, nout=F_, K=F_),
-                          dict(dY=gEQ, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvq, rows=N * D, nout=Fe, K=F_)]
-                if cfg.htr_mode & 1:
-                    probs.append(dict(dY=gEK, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvk[0], rows=N * D, nout=Fe, K=F_))
-                else:
-                    off = 0
-                    for l in range(1, lmax + 1):
-                        cnt = 2 * l + 1
-                        probs.append(dict(dY=gEK, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvk[l - 1], rows=N * cnt, nout=Fe, K=F_,
-                                          rowmap=(cnt, D, off)))
-                        off += cnt
-            weight_grad_group(probs)
-        # ---- gX1 = gX + gXp W_vu (+ gEQ W_vq + gEK_l W_vk_l)
-        joint = bool(cfg.htr_mode & 1)
-        if last:
-            gemm(gXp, F_, _T(lw, "Wvu"), None, gX1, F_, N * D, F_, F_, res=gX)
-        elif Fe == F_:
-            # one launch; per degree block: A = [gXp | gEQ | gEK] (K-segmented), W = [W_vu^T | W_vq^T | W_vk_l^T] along K
-            probs, off = [], 0
-            for l in range(1, lmax + 1):
-                cnt = D if joint else 2 * l + 1
-                wcat = lw.T.get(("Xcat", l))
-                if wcat is None:
-                    wcat = torch.cat([_T(lw, "Wvu"), _T(lw, "Wvq"), lw.Wvk[l - 1].t()], dim=1).contiguous()
-                    lw.T[("Xcat", l)] = wcat
-                probs.append(dict(A=gXp, A2=gEQ, A3=gEK, a_seg=F_, lda=F_, W=wcat, C=gX1, ldc=F_, rows=N * cnt,
-                                  nout=F_, K=3 * F_, rowmap=(cnt, D, off), res=gX))
-                off += cnt
-                if joint:
-                    break
-            gemm_group(probs)
-        else:                                      # evec_dim != F: three chained products
-            gemm(gXp, F_, _T(lw, "Wvu"), None, gX1, F_, N * D, F_, F_, res=gX)
-            gemm(gEQ, Fe, _T(lw, "Wvq"), None, gX1, F_, N * D, F_, Fe, res=gX1)
-            off = 0
-            for l in range(1, lmax + 1):
-                cnt = D if joint else 2 * l + 1
-                wkT = lw.T.get(("Wvk", l))
-                if wkT is None:
-                    wkT = lw.Wvk[l - 1].t().contiguous()
-                    lw.T[("Wvk", l)] = wkT
-                gemm(gEK, Fe, wkT, None, gX1, F_, N * cnt, F_, Fe, rowmap=(cnt, D, off), res=gX1)
-                off += cnt
-                if joint:
-                    break
+            snap("layer", li, h=wb.gh, X=wb.gX if wb.gX is not None else torch.zeros((N, D, F_), **f32),
+                 t=wb.gt if wb.gt is not None else torch.zeros((E, F_), **f32))
+        gt_in = _eqff_htr_backward(p, lw, lt, wb, li, eq_fused, gw)
         if snap is not None:
-            snap("message", li, h=gh1, X=gX1)
-        # ---- message backward
-        if first and G > 1:                        # one launch instead of G degree groups: one g_cut slice is written
-            g_cut_parts[G * li + 1:G * li + G].zero_()       # (never together with wide slots: zero_X_in excludes them)
-        call("gn_message_backward", ptr(lt.xs), ptr(lt.vs), M * F_, ptr(lt.eproj), lde, ptr(lt.attn),
-             ptr(lt.nproj), 4 * F_, None if first else ptr(lt.X_in), ptr(g.rl), ptr(g.cut), ptr(g.outdeg),
-             ptr(gh1), ptr(gX1), ptr(g.rowptr), ptr(g.src), ptr(g.tgt_by_src), ptr(colptr), ptr(perm),
-             ptr(g_eproj), ptr(g_s), ptr(g_nproj), 4 * F_, ptr(g_x), ptr(g_v), None if first else ptr(gX2),
-             rl_slice(Wm * li), cut_slice(Wm * G * li),
-             None if (MSG_BWD_PAIR and (first or G == 1)) else ptr(ga_parts), E,
-             N, F_, H, cfg.lmax_arg_msg_bwd, int(cfg.sep_dir), int(cfg.sep_tensor), cfg.act, _stream())
-        # the edge-sized W_e^T product leaves 0.7 of its last tile round idle: the two K-heavy atom-sized products
-        # (g_x W_s2, g_v W_v2; 60 us as a launch of their own) ride there; W_n1^T needs their output and follows alone
-        if first:                                  # the tensor-gate columns of g_eproj were not written: K-prefix
-            _, _, ke = _We_first(cfg, lw)
-            _value_first(cfg, lw)                  # (Ws20 / Wv20 exist before the group below names them)
-        gemm_group([dict(A=g_eproj, lda=lde, W=_T(lw, "We0" if first else "We"), C=gt_b, ldc=F_, rows=E, nout=F_,
-                         K=ke if first else lde, res=gt_in),
-                    dict(A=g_x, lda=M * F_, W=_T(lw, "Ws20" if first else "Ws2"), C=g_nproj, ldc=4 * F_, rows=N, nout=F_,
-                         K=_value_first(cfg, lw) if first else M * F_, c_off=2 * F_, dgate=lt.nproj, g_off=2 * F_),
-                    dict(A=g_v, lda=M * F_, W=_T(lw, "Wv20" if first else "Wv2"), C=g_nproj, ldc=4 * F_, rows=N, nout=F_,
-                         K=_value_first(cfg, lw) if first else M * F_,
-                         c_off=3 * F_, dgate=lt.nproj, g_off=3 * F_),
-                    # the q | k half of the W_n1^T product needs only the message backward's g_q | g_k: it rides here
-                    # too and halves the K of the product that has to wait for the two riders above (33 -> 20 us)
-                    dict(A=g_nproj, lda=4 * F_, W=_Tqk(lw), C=gh_qk, ldc=F_, rows=N, nout=F_, K=2 * F_, res=gh1)])
-        gemm(g_nproj, 4 * F_, _Tsv(lw), None, gh2, F_, N, F_, 2 * F_, res=gh_qk, a_off=2 * F_)
-        if pgrads is not None:                     # g_eproj, g_nproj, g_x, g_v are final; the next layer reuses them
-            gw = pgrads.layers[li]
-            ne = ke if first else lde               # layer 0 with zero X_in: the tensor-gate rows get exactly zero
-            nv = _value_first(cfg, lw) if first else M * F_
-            weight_grad_group([
-                dict(dY=g_eproj, ldy=lde, A=lt.t_in, lda=F_, dW=gw.We, db=gw.be, rows=E, nout=ne, K=F_),
-                dict(dY=g_nproj, ldy=4 * F_, A=lt.h_in, lda=F_, dW=gw.Wn1, db=gw.bn1, rows=N, nout=4 * F_, K=F_),
-                dict(dY=g_x, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=2 * F_, dW=gw.Ws2, db=gw.bs2, rows=N, nout=nv, K=F_),
-                dict(dY=g_v, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=3 * F_, dW=gw.Wv2, db=gw.bv2, rows=N, nout=nv, K=F_)])
-            if ne < lde:
-                gw.We[ne:].zero_()
-                gw.be[ne:].zero_()
-            if nv < M * F_:
-                for t_ in (gw.Ws2, gw.bs2, gw.Wv2, gw.bv2):
-                    t_[nv:].zero_()
-        gh, gh2 = gh2, gh
-        gX, gX2 = gX2, gX
-        if gh2 is gh_caller:
-            gh2 = new(N, F_)
-        if gX2 is gX_caller:
-            gX2 = new(N, D, F_)
-        gt, gt_b = gt_b, (gt if gt is not None else new(E, F_))
+            snap("message", li, h=wb.gh1, X=wb.gX1)
+        _gata_backward(p, lw, lt, wb, li, gt_in, gw)
+        # the layer's input adjoints become the current ones; the caller's tensors leave the rotation
+        wb.gh, wb.gh2 = wb.gh2, wb.gh
+        wb.gX, wb.gX2 = wb.gX2, wb.gX
+        if wb.gh2 is gh_caller:
+            wb.gh2 = new(N, F_)
+        if wb.gX2 is gX_caller:
+            wb.gX2 = new(N, D, F_)
+        wb.gt, wb.gt_b = wb.gt_b, (wb.gt if wb.gt is not None else new(E, F_))
         if snap is not None and (cfg.layernorm or cfg.steerable_norm):
-            snap("norm", li, h=gh, X=None if first else gX)
+            snap("norm", li, h=wb.gh, X=None if lt.first else wb.gX)
         # ---- optional input norms (gotennet.py:397-398): back to the un-normalised h / X
         if cfg.layernorm:
-            if pgrads is not None:                 # gh: dL/d of the normalised h
-                layernorm_param_grad(lt.h_raw, lw.ln_w, lw.ln_b, gh, _lib.ACT_NONE, pgrads.layers[li].ln_w,
-                                     pgrads.layers[li].ln_b)
-            if pw.emb_idx is None:
-                call("gn_layernorm_backward", ptr(lt.h_raw), ptr(lw.ln_w), 1e-5, ptr(gh), N, F_, ptr(gh2), _stream())
-            else:                                  # statistics over the real channels: compact -> kernel -> padded layout
-                gc = torch.empty((N, cfg.F_model), **f32)
-                xc, gyc = lt.h_raw.index_select(1, pw.emb_idx), gh.index_select(1, pw.emb_idx)   # (named: alive until the launch)
-                call("gn_layernorm_backward", ptr(xc), ptr(lw.ln_w), 1e-5, ptr(gyc), N, cfg.F_model, ptr(gc), _stream())
-                gh2.zero_().index_copy_(1, pw.emb_idx, gc)
-            gh, gh2 = gh2, gh
+            if gw is not None:                     # gh: dL/d of the normalised h
+                layernorm_param_grad(lt.h_raw, lw.ln_w, lw.ln_b, wb.gh, _lib.ACT_NONE, gw.ln_w, gw.ln_b)
+            _norm_h_backward(lw, lt.h_raw, wb.gh, wb.gh2, pw.emb_idx)
+            wb.gh, wb.gh2 = wb.gh2, wb.gh
         if cfg.steerable_norm:
-            if pw.emb_idx is None:
-                call("gn_tensor_norm_backward", ptr(lt.X_raw), ptr(lw.tln_w), ptr(gX), 1e-12, N, F_, lmax, ptr(gX2), _stream())
-            else:
-                gc = torch.empty((N, D, cfg.F_model), **f32)
-                xc, gyc = lt.X_raw.index_select(2, pw.emb_idx), gX.index_select(2, pw.emb_idx)
-                call("gn_tensor_norm_backward", ptr(xc), ptr(lw.tln_w), ptr(gyc), 1e-12, N, cfg.F_model, lmax, ptr(gc), _stream())
-                gX2.zero_().index_copy_(2, pw.emb_idx, gc)
-            gX, gX2 = gX2, gX
+            _norm_X_backward(lw, lt.X_raw, wb.gX, wb.gX2, cfg.lmax, pw.emb_idx)
+            wb.gX, wb.gX2 = wb.gX2, wb.gX
 
-    # ---- init backward (layers.py:1658-1714) ------------------------------------------
-    g_feat = new(E, 2 * F_)
-    call("gn_edge_init_backward", ptr(gt), ptr(tape.h0), ptr(tape.feat), 2 * F_, ptr(g.rowptr), ptr(g.src),
-         ptr(colptr), ptr(perm), N, F_, ptr(g_feat), ptr(gh), _stream())
-    Fc = cfg.Fc or F_
-    gy = new(N, Fc)
-    gemm(gh, F_, _T(pw, "Wb"), None, gy, Fc, N, Fc, F_)
-    gy1 = new(N, Fc)
-    call("gn_layernorm_silu_backward", ptr(tape.y_pre), ptr(pw.ln_w), ptr(pw.ln_b), 1e-5, ptr(gy), N, Fc, ptr(gy1), cfg.act, _stream())
-    gemm(gy1, Fc, _T(pw, "Wa"), None, g_ctx, 2 * F_, N, 2 * F_, Fc)
-    call("gn_node_init_backward", ptr(g_ctx), ptr(z32), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(pw.A_nbr),
-         ptr(g.rowptr), ptr(g.src), N, F_, ptr(g_feat), cut_slice(Wm * G * L), _stream())
+    g_feat, gy, gy1 = _init_backward(p, pw, z32, tape, wb, new)
     if pgrads is not None:
-        layernorm_param_grad(tape.y_pre, pw.ln_w, pw.ln_b, gy, cfg.act, pgrads.ln_w, pgrads.ln_b)
-        weight_grad_group([dict(dY=gh, ldy=F_, A=tape.y, lda=Fc, dW=pgrads.Wb, db=pgrads.bb, rows=N, nout=F_, K=Fc),
-                           dict(dY=gy1, ldy=Fc, A=tape.ctx0, lda=2 * F_, dW=pgrads.Wa, db=pgrads.ba, rows=N, nout=Fc, K=2 * F_),
-                           dict(dY=g_feat, ldy=2 * F_, A=g.phi, lda=R, dW=pgrads.Winit, db=pgrads.binit, rows=E, nout=2 * F_,
-                                K=R)])
-        # species order of the atoms (integer plumbing): a stable argsort of z and the first sorted position of each species
-        n_sp = pw.A_na.shape[0]
-        zs, order = torch.sort(z32.long(), stable=True)
-        sp_ptr = torch.searchsorted(zs, torch.arange(n_sp + 1, device=zs.device)).to(torch.int32)
-        order = order.to(torch.int32)
-        per_src = new(N, F_)                       # per-source sums of the A_nbr gradient (named: alive until the launch)
-        call("gn_embedding_grad", ptr(g_ctx), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(g.dst), ptr(colptr), ptr(perm),
-             ptr(order), ptr(sp_ptr), n_sp, N, F_, ptr(per_src), ptr(pgrads.A_na), ptr(pgrads.A_nbr), _stream())
+        _init_weight_grads(cfg, pw, pgrads, z32, g, tape, wb, g_feat, gy, gy1, new)
         if not geometry:
             return None, None
     g_phi = new(E, R)
-    gemm(g_feat, 2 * F_, _T(pw, "Winit"), None, g_phi, R, E, R, 2 * F_)
+    p.gemm(g_feat, 2 * F_, _T(pw, "Winit"), None, g_phi, R, E, R, 2 * F_)
     g_vec, g_diff = new(E, 3), new(E)
-    call("gn_edge_geometry_backward", ptr(g.edge_vec), ptr(g.edge_diff), ptr(g.src), ptr(g.dst), E, lmax, R,
-         cfg.basis, ptr(pw.rb0), ptr(pw.rb1), float(cfg.cutoff), ptr(g_rl_parts), n_rl, ptr(g_cut_parts), n_cut,
-         ptr(g_phi), ptr(g_vec), ptr(g_diff), _stream())
+    call("gn_edge_geometry_backward", ptr(g.edge_vec), ptr(g.edge_diff), ptr(g.src), ptr(g.dst), E, cfg.lmax, R,
+         cfg.basis, ptr(pw.rb0), ptr(pw.rb1), float(cfg.cutoff), ptr(wb.g_rl_parts), wb.n_rl, ptr(wb.g_cut_parts), wb.n_cut,
+         ptr(g_phi), ptr(g_vec), ptr(g_diff), p.st)
     if snap is not None:
-        snap("init", -1, h=gh, t=gt, phi=g_phi, X=None if zero_X_in(cfg, 0) else gX, vec=g_vec, diff=g_diff)
+        snap("init", -1, h=wb.gh, t=wb.gt, phi=g_phi, X=None if tape.layers and tape.layers[0].first else wb.gX, vec=g_vec,
+             diff=g_diff)
     return g_vec, g_diff
 
 
@@ -1140,6 +1143,3 @@ def pos_gradient(g: Graph, g_vec: torch.Tensor, g_diff: torch.Tensor, sign: floa
     call("gn_pos_scatter", ptr(g_vec), ptr(g_diff), ptr(g.edge_vec), ptr(g.rowptr), ptr(colptr), ptr(perm),
          g.N, float(sign), ptr(out), _stream())
     return out
-
-
-forward, backward, gata_layer, eqff_layer = _forward_impl, _backward_impl, _gata_layer_impl, _eqff_layer_impl

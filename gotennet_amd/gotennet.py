@@ -236,7 +236,7 @@ def _pack_gata(gata) -> engine.LayerWeights:
 def _pack_eqff(eq, lw: Optional[engine.LayerWeights] = None) -> engine.LayerWeights:
     d = lambda t: t.detach().contiguous()
     if lw is None:
-        lw = engine.LayerWeights(*([None] * 8))
+        lw = engine.LayerWeights()
     lw.Wvu = d(eq.W_vu.weight)
     lw.Wm0, lw.bm0 = d(eq.gamma_m[0].weight), d(eq.gamma_m[0].bias)
     lw.Wm1, lw.bm1 = d(eq.gamma_m[1].weight), d(eq.gamma_m[1].bias)
