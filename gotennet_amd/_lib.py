@@ -14,7 +14,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GN_LIB_PATH") or os.path.join(_PKG, "libgotennet_hip.so")
 
 GN_ERR_BAD_ARG = 10001
-ABI_VERSION = 9
+ABI_VERSION = 10
 LMAX_SLICED = 0x100      # GN_LMAX_SLICED: OR-ed into the lmax argument of the message / HTR entry points
 LMAX_MEAN, LMAX_MAX = 0x200, 0x400      # GN_LMAX_MEAN / GN_LMAX_MAX: the reference's aggr = "mean" / "max" (message entries)
 
@@ -29,7 +29,7 @@ class GemmDesc(C.Structure):
                 ("row_cnt", _I), ("row_gstride", _I), ("row_goff", _I),
                 ("res", _P), ("gate", _P), ("gate_mode", _I), ("pre_out", _P),
                 ("pro_mode", _I), ("pro_lo", _I), ("pro_hi", _I), ("a_pre", _P), ("ldp", _I),
-                ("a_gate", _P), ("ldg", _I), ("A2", _P), ("A3", _P), ("a_seg", _I), ("act_kind", _I)]
+                ("a_gate", _P), ("ldg", _I), ("A2", _P), ("A3", _P), ("a_seg", _I), ("act_kind", _I), ("lda2", _I)]
 
 
 class WgradDesc(C.Structure):

@@ -16,11 +16,13 @@ struct GemmArgs {
     int pro_mode, pro_lo, pro_hi;
     int row_cnt, row_gstride, row_goff;
     int gate_mode;                  // 0: value * gate; 1: value * SiLU'(gate)
-    // K-segmented A operand: columns [s * a_seg, (s+1) * a_seg) of the logical A come from A / A2 / A3 (same lda,
-    // same row addressing): sums up to three products that share their output rows.  a_seg = 0: plain A.
+    // K-segmented A operand: columns [s * a_seg, (s+1) * a_seg) of the logical A come from A / A2 / A3 (same row
+    // addressing; A with leading dimension lda, A2 and A3 with lda2, below): sums up to three products that share their
+    // output rows.  The last segment may be narrower than a_seg (K < 2 a_seg or < 3 a_seg).  a_seg = 0: plain A.
     const float* A2; const float* A3; int a_seg;
     int nt_store;                   // first output column written with non-temporal stores (outputs far larger than the L2s; INT_MAX: none)
     int act_kind;                   // GN_ACT_*: the activation of the epilogue columns, of gate_mode 1 and of the prologues
+    int lda2;                       // leading dimension of A2 / A3 (the launcher resolves the descriptor's 0 to lda)
 };
 
 constexpr int GN_MAX_GROUP = 4;

@@ -181,14 +181,19 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
         const int kc = kok ? kraw : 0;               // clamped: any valid column, zeroed by select in stashA
         const int k0c = kok ? k0 : 0;
         const float* Ab = p.A;
-        int ka = kc;
+        int ka = kc, ld = p.lda;
         if (p.a_seg) {
             const bool s2 = k0c >= 2 * p.a_seg, s1 = k0c >= p.a_seg;
             Ab = s2 ? p.A3 : (s1 ? p.A2 : p.A);
             ka = kc - (s2 ? 2 * p.a_seg : (s1 ? p.a_seg : 0));
+            // the segment's leading dimension goes with its base pointer (mask arithmetic: a select between two descriptor
+            // fields is turned into an indexed load from a private copy, which then lives in scratch).  With ld a per-slab value
+            // the row offsets prow * ld are no longer hoisted out of the K loop: one v_mad_i64_i32 per row and slab in place of
+            // a 64-bit add, eight registers less (profiles/dt_kcat_ab.txt)
+            ld = p.lda + ((p.lda2 - p.lda) & -(int)s1);
         }
 #pragma unroll
-        for (int i = 0; i < RA; ++i) qa[i] = ld4(Ab + (size_t)prow[i] * p.lda + ka);   // prow of a row past M is row 0: valid memory
+        for (int i = 0; i < RA; ++i) qa[i] = ld4(Ab + (size_t)prow[i] * ld + ka);   // prow of a row past M is row 0: valid memory
         kflag = kok;
     };
     // F16: scale this wave's 8-row block of every M-tile by 2^-e (e = running maximum of the block's binary exponent
@@ -262,16 +267,16 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
         const bool pro = PRO && p.pro_mode && kc >= p.pro_lo && kc < p.pro_hi;
         // K-segmented A (a slab never straddles a segment: a_seg % BK == 0, checked by the launcher)
         const float* Ab = p.A;
-        int ka = kc;
+        int ka = kc, ld = p.lda;
         if (p.a_seg) {
-            if (k0 >= 2 * p.a_seg) { Ab = p.A3; ka = kc - 2 * p.a_seg; }
-            else if (k0 >= p.a_seg) { Ab = p.A2; ka = kc - p.a_seg; }
+            if (k0 >= 2 * p.a_seg) { Ab = p.A3; ka = kc - 2 * p.a_seg; ld = p.lda2; }
+            else if (k0 >= p.a_seg) { Ab = p.A2; ka = kc - p.a_seg; ld = p.lda2; }
         }
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             float4 v = zero4();
             if (aok[i] && kok) {
-                v = ld4(Ab + (size_t)prow[i] * p.lda + ka);
+                v = ld4(Ab + (size_t)prow[i] * ld + ka);
                 if constexpr (PRO) {
                     if (pro) v = (p.pro_mode == 1) ? act4(v, ASILU ? (int)GN_ACT_SILU : p.act_kind) : v * dact4(ld4(p.a_pre + (size_t)prow[i] * p.ldp + kc), ASILU ? (int)GN_ACT_SILU : p.act_kind);
                     if (p.a_gate) v = v * ld4(p.a_gate + (size_t)prow[i] * p.ldg + kc);
@@ -685,7 +690,7 @@ static int gemm_group_impl(const gn_gemm_desc* d, int n, void* stream, int split
                           q.pro_mode, q.pro_lo, q.pro_hi, q.a_pre, q.ldp, q.a_gate, q.ldg))
             return GN_ERR_BAD_ARG;
         if (q.a_seg < 0 || (q.a_seg && ((q.a_seg % gn::BK) || q.pro_mode || q.a_gate || q.K > 3 * q.a_seg ||
-                                        !q.A2 || (q.K > 2 * q.a_seg && !q.A3))))
+                                        !q.A2 || (q.K > 2 * q.a_seg && !q.A3) || q.lda2 < 0 || (q.lda2 & 3))))
             return GN_ERR_BAD_ARG;
         if (q.M == 0) continue;
         g[m++] = gn::GemmArgs{q.A, q.W, q.bias, q.C, q.res, q.gate, q.pre_out, q.a_pre, q.a_gate, q.lda, q.ldc, q.ldp,
@@ -693,6 +698,7 @@ static int gemm_group_impl(const gn_gemm_desc* d, int n, void* stream, int split
                               q.row_gstride, q.row_goff, q.gate_mode, q.A2, q.A3, q.a_seg};
         if (q.act_kind < 0 || q.act_kind >= GN_ACT_COUNT) return GN_ERR_BAD_ARG;
         g[m - 1].act_kind = q.act_kind;
+        g[m - 1].lda2 = q.lda2 ? q.lda2 : q.lda;       // 0: A2 / A3 share A's leading dimension
     }
     if (m == 0) return GN_OK;
     return gn_gemm_launch(g, m, (hipStream_t)stream, split);

@@ -100,20 +100,24 @@ __global__ __launch_bounds__(256) void gemm_f16x2_panel(const GroupArgs ga) {
     const int c = lane & 31, lr = lane >> 5;
     float4 va[NPS][KC];
     bool aok[NPS];
-    size_t ro[NPS];
+    size_t ro[NPS], ro2[NPS];                        // row offsets in A and in A2 / A3 (their own leading dimension)
     if (p.row_cnt == 1) {                            // identity row map (wave-uniform branch: no per-row division code)
 #pragma unroll
         for (int ps = 0; ps < NPS; ++ps) {
             const int r = m0 + 8 * wave + ps * 2 + lr;
             aok[ps] = r < p.M;
-            ro[ps] = (size_t)((aok[ps] ? r : 0) * p.row_gstride + p.row_goff) * p.lda;       // a row past M: row 0, zeroed below
+            const size_t pr = (size_t)((aok[ps] ? r : 0) * p.row_gstride + p.row_goff);      // a row past M: row 0, zeroed below
+            ro[ps] = pr * p.lda;
+            ro2[ps] = pr * p.lda2;
         }
     } else {
 #pragma unroll
         for (int ps = 0; ps < NPS; ++ps) {
             const int r = m0 + 8 * wave + ps * 2 + lr;
             aok[ps] = r < p.M;
-            ro[ps] = (size_t)phys_row(p, aok[ps] ? r : 0) * p.lda;
+            const size_t pr = (size_t)phys_row(p, aok[ps] ? r : 0);
+            ro[ps] = pr * p.lda;
+            ro2[ps] = pr * p.lda2;
         }
     }
     // K-segmented A: a 128-column piece never straddles a segment (a_seg % 128 == 0: launcher)
@@ -125,7 +129,7 @@ __global__ __launch_bounds__(256) void gemm_f16x2_panel(const GroupArgs ga) {
             const unsigned long long a0 = (unsigned long long)seg_ptr[0], a1 = (unsigned long long)seg_ptr[1], a2 = (unsigned long long)seg_ptr[2];
             const float* Ak = reinterpret_cast<const float*>(s2 ? a2 : (s1 ? a1 : a0)) + (k - (s2 ? 2 * a_seg : (s1 ? a_seg : 0))) + 4 * c;
 #pragma unroll
-            for (int ps = 0; ps < NPS; ++ps) va[ps][kc] = ld4(Ak + ro[ps]);
+            for (int ps = 0; ps < NPS; ++ps) va[ps][kc] = ld4(Ak + (s1 ? ro2[ps] : ro[ps]));
         }
     };
     fetch_chunk(0);

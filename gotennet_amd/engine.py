@@ -66,6 +66,9 @@ ZERO_X_FIRST = os.environ.get("GN_ZERO_X_FIRST", "1") != "0"
 #: test switch: True withholds the head-sum workspace from gn_message_backward where the entry point allows it (monolithic
 #: launches and every first interaction), which then runs the by-target / by-source kernel pair instead of the merged kernel
 MSG_BWD_PAIR = False
+#: A/B and test switch: False forms dL/dt of a layer with a plain edge update in two edge-sized launches (gt_a = gt + g_pre_t Wt^T
+#: in ``_eqff_htr_backward``, then gt_b = gt_a + g_eproj We^T) instead of the one K-concatenated launch of ``_gata_backward``
+DT_KCAT = True
 
 
 def zero_X_in(cfg: "Config", li: int) -> bool:
@@ -282,6 +285,7 @@ def gemm_group(problems, mode=None, kind=None):
             d.a_gate = ptr(g("a_gate")); d.ldg = g("ldg", 0)
             d.A2, d.A3, d.a_seg = ptr(g("A2")), ptr(g("A3")), g("a_seg", 0)
             d.act_kind = g("kind", kind)
+            d.lda2 = g("lda2", 0)
         call(_PLANE_MODES[mode][1] if split else "gn_gemm_group", arr, len(chunk), _stream())
 
 
@@ -865,6 +869,15 @@ class _BackwardWork:
     G: int; msg_rl: int; msg_cut: int; init_cut: int; htr_rl: dict; n_rl: int; n_cut: int
     gm: Any; gXp: Any; g_g1: Any; g_ctx: Any; gh1: Any; gX1: Any; gh2: Any; gX2: Any; gh_qk: Any; gEQ: Any; gEK: Any
     g_eproj: Any; g_s: Any; g_nproj: Any; g_x: Any; g_v: Any; gt_a: Any; gt_b: Any; g_pre_t: Any
+    dt_kcat: bool = False                          # dL/dt = gt + [g_eproj | g_pre_t] [We | Wt]^T in ONE launch (``_dt_kcat``)
+
+
+def _dt_kcat(cfg: Config) -> bool:
+    """A layer with a plain edge update states dL/dt of its input ONCE, as a product over the concatenated K of g_eproj and
+    g_pre_t (``_gata_backward``).  Not with ``composed_update`` (its gamma_t backward is a chain of its own), nor where the
+    K-prefix of g_eproj is no whole number of K-slabs (the segment boundary of the projection kernels)."""
+    n = cfg.lmax if cfg.sep_dir else 1
+    return DT_KCAT and not cfg.composed_update and ((2 + n) * cfg.F) % 32 == 0 and ((1 + cfg.M) * cfg.F) % 32 == 0
 
 
 def _backward_work(cfg: Config, pw: PackedWeights, g: Graph, f32: dict, gh, gX, eq_fused: bool) -> _BackwardWork:
@@ -881,6 +894,7 @@ def _backward_work(cfg: Config, pw: PackedWeights, g: Graph, f32: dict, gh, gX, 
         gX = torch.zeros((N, D, F_), **f32)
     lay = _partial_sum_layout(cfg, pw)
     colptr, perm = g.csc()
+    kcat = _dt_kcat(cfg)
     return _BackwardWork(
         # dL/d of the current layer's output h, X (None = 0), t (None = 0: nothing above the last layer reads t): rotate per layer
         gh=gh.contiguous(), gX=None if gX is None else gX.contiguous(), gt=None, colptr=colptr, perm=perm, **lay,
@@ -893,14 +907,16 @@ def _backward_work(cfg: Config, pw: PackedWeights, g: Graph, f32: dict, gh, gX, 
         gh2=new(N, F_), gX2=new(N, D, F_), gh_qk=new(N, F_),     # dL/d of the layer's input (gh_qk: its q | k part)
         gEQ=new(N, D, Fe), gEK=new(N, D, Fe),          # HTR
         g_eproj=new(E, (1 + M) * F_), g_s=new(E, H), g_nproj=new(N, 4 * F_), g_x=new(N, M * F_), g_v=new(N, M * F_),   # message backward
-        gt_a=new(E, F_), gt_b=new(E, F_), g_pre_t=new(E, F_))   # dL/dt after the edge update / of the layer input; dL/d pre_t
+        # dL/dt after the edge update (only where it is a tensor of its own) / of the layer input; dL/d pre_t
+        gt_a=None if kcat else new(E, F_), gt_b=new(E, F_), g_pre_t=new(E, F_), dt_kcat=kcat)
 
 
 def _eqff_htr_backward(p: _Call, lw: LayerWeights, lt: LayerTape, wb: _BackwardWork, li: int, eq_fused: bool, gw):
     """EQFF backward (reads gh, gX: writes gXp, gh1 -- and gm, g_g1, g_ctx un-fused); independent of it, the HTR + edge-update
     backward of a layer that has one (reads gt: writes gEQ, gEK, g_pre_t, gt_a, the layer's HTR slice of dL/drl); then the
     X-products' (gX1 = dL/dX at the message stage's output).  ``gw``: the layer's parameter-gradient storage or None.
-    -> dL/dt at the layer's message stage (gt_a, or gt itself where t passes through unchanged)."""
+    -> dL/dt at the layer's message stage (gt_a, or gt itself where t passes through unchanged -- and with ``wb.dt_kcat``,
+    where the edge update's term g_pre_t Wt^T is left to the K-concatenated launch of ``_gata_backward``)."""
     cfg, g, st, F_, D, Fe, N, E = p.cfg, p.g, p.st, p.F, p.D, p.Fe, p.N, p.E
     gh, gX, gt = wb.gh, wb.gX, wb.gt
     m1 = None
@@ -929,9 +945,12 @@ def _eqff_htr_backward(p: _Call, lw: LayerWeights, lt: LayerTape, wb: _BackwardW
             call("gn_htr_backward", ptr(gt), ptr(lt.pre_t), ptr(lt.w), ptr(lt.w_raw), ptr(lt.EQ), ptr(lt.EK),
                  ptr(g.rl), ptr(g.rowptr), ptr(g.src), ptr(g.tgt_by_src), ptr(wb.colptr), ptr(wb.perm), N, Fe, cfg.lmax_arg_bwd,
                  cfg.htr_mode, ptr(wb.gEQ), ptr(wb.gEK), rl_slice, ptr(wb.g_pre_t), cfg.act, st)
-            # gt_a = gt + ((gt * w) * SiLU'(pre_t)) Wt; the atom-sized gamma_m product rides in its launch
-            p.group([dict(A=wb.g_pre_t, lda=F_, W=_T(lw, "Wt"), C=wb.gt_a, ldc=F_, rows=E, nout=F_, K=F_, res=gt), m1])
-        gt_in = wb.gt_a
+            if wb.dt_kcat:                         # g_pre_t Wt^T joins g_eproj We^T in _gata_backward; gamma_m's product alone
+                p.group([m1])
+            else:
+                # gt_a = gt + ((gt * w) * SiLU'(pre_t)) Wt; the atom-sized gamma_m product rides in its launch
+                p.group([dict(A=wb.g_pre_t, lda=F_, W=_T(lw, "Wt"), C=wb.gt_a, ldc=F_, rows=E, nout=F_, K=F_, res=gt), m1])
+        gt_in = gt if wb.dt_kcat else wb.gt_a
     if not eq_fused:                               # EQFF backward, second half
         p.gemm(wb.g_g1, F_, _T(lw, "Wm0"), None, wb.g_ctx, 2 * F_, N, 2 * F_, F_)
         call("gn_eqff_backward_b", ptr(wb.g_ctx), ptr(lt.ctx), ptr(lt.Xp), ptr(gh), N, F_, D, ptr(wb.gXp), ptr(wb.gh1), st)
@@ -992,7 +1011,15 @@ def _gata_backward(p: _Call, lw: LayerWeights, lt: LayerTape, wb: _BackwardWork,
     # A zero-X_in layer: the tensor-gate columns of g_eproj, g_x, g_v were not written -- K-prefixes
     ke, kv = p.cols[first]
     g_nproj = wb.g_nproj
-    p.group([dict(A=wb.g_eproj, lda=lde, W=_T(lw, "We", 0, ke), C=wb.gt_b, ldc=F_, rows=E, nout=F_, K=ke, res=gt_in),
+    if wb.dt_kcat and lw.Wt is not None:
+        # dL/dt stated once: gt_b = gt + [g_eproj | g_pre_t] [We^T | Wt^T]^T, one product over the concatenated K (A2 = g_pre_t
+        # has a leading dimension of its own); the message backward above never read the edge update's half
+        wdt = derived(lw, ("dtcat", ke), lambda: torch.cat([_T(lw, "We", 0, ke), _T(lw, "Wt")], 1).contiguous())
+        dt = dict(A=wb.g_eproj, lda=lde, A2=wb.g_pre_t, lda2=F_, a_seg=ke, W=wdt, C=wb.gt_b, ldc=F_, rows=E, nout=F_,
+                  K=ke + F_, res=gt_in)
+    else:
+        dt = dict(A=wb.g_eproj, lda=lde, W=_T(lw, "We", 0, ke), C=wb.gt_b, ldc=F_, rows=E, nout=F_, K=ke, res=gt_in)
+    p.group([dt,
              dict(A=wb.g_x, lda=M * F_, W=_T(lw, "Ws2", 0, kv), C=g_nproj, ldc=4 * F_, rows=N, nout=F_, K=kv, c_off=2 * F_,
                   dgate=lt.nproj, g_off=2 * F_),
              dict(A=wb.g_v, lda=M * F_, W=_T(lw, "Wv2", 0, kv), C=g_nproj, ldc=4 * F_, rows=N, nout=F_, K=kv, c_off=3 * F_,

@@ -38,7 +38,7 @@ extern "C" {
 
 #define GN_OK 0
 #define GN_ERR_BAD_ARG 10001     /* shape/flag combination the kernels do not implement */
-#define GN_ABI_VERSION 9
+#define GN_ABI_VERSION 10
 /* OR-ed into the `lmax` ARGUMENT of gn_message_aggregate, gn_message_backward(_groups), gn_htr_edge and
  * gn_htr_backward: run this call on the degree-sliced kernel family at lmax <= 4 as well (the family that serves
  * lmax 5..8).  An explicit per-call request -- the library reads no environment variable and keeps no switch; every
@@ -176,10 +176,13 @@ typedef struct gn_gemm_desc {
     const float* a_pre; int ldp;
     const float* a_gate; int ldg;
     /* K-segmented A: when a_seg != 0 the logical A columns [s a_seg, (s+1) a_seg) come from A, A2, A3 (s = 0, 1, 2;
-     * same lda and row addressing; a_seg % 32 == 0; no prologue): C = res + A W_0^T + A2 W_1^T + A3 W_2^T with the
-     * three weights concatenated along K.  Used for gX = gX + gXp W_vu + gEQ W_vq + gEK_l W_vk_l. */
+     * same row addressing; a_seg % 32 == 0; no prologue): C = res + A W_0^T + A2 W_1^T + A3 W_2^T with the
+     * weights concatenated along K.  The last segment may be narrower than a_seg (a_seg < K <= 2 a_seg: two segments;
+     * 2 a_seg < K <= 3 a_seg: three).  Used for gX = gX + gXp W_vu + gEQ W_vq + gEK_l W_vk_l and, with lda2, for
+     * dL/dt = gt + g_eproj W_e + g_pre_t W_t. */
     const float* A2; const float* A3; int a_seg;
     int act_kind;                /* GN_ACT_*: activation of the [act_lo, act_hi) columns, of gate_mode 1 and of the prologues */
+    int lda2;                    /* leading dimension of A2 and A3 (a multiple of 4); 0: the same as lda */
 } gn_gemm_desc;
 int gn_gemm_group(const gn_gemm_desc* problems, int n, void* stream);
 
