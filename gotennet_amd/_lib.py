@@ -14,12 +14,12 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GN_LIB_PATH") or os.path.join(_PKG, "libgotennet_hip.so")
 
 GN_ERR_BAD_ARG = 10001
-ABI_VERSION = 10
+ABI_VERSION = 11
 LMAX_SLICED = 0x100      # GN_LMAX_SLICED: OR-ed into the lmax argument of the message / HTR entry points
 LMAX_MEAN, LMAX_MAX = 0x200, 0x400      # GN_LMAX_MEAN / GN_LMAX_MAX: the reference's aggr = "mean" / "max" (message entries)
 
 ACT_NONE = 11            # GN_ACT_NONE
-_P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_long
+_P, _I, _F, _L, _D = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 
 # symbol -> argtypes (mirrors include/gotennet_hip.h one for one)
 class GemmDesc(C.Structure):
@@ -55,6 +55,8 @@ SIGNATURES = {
     "gn_tensor_norm": [_P, _P, _F, _I, _I, _I, _P, _P],
     "gn_gemm": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gn_attn_softmax": [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P],
+    "gn_attn_softmax_dropout": [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _D, _I, _P],
+    "gn_attn_dropout_mask": [_P, _I, _D, _L, _I, _P, _P],
     "gn_message_aggregate": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "gn_eqff_fused_supported": [_I, _I, _I],
     "gn_eqff_fused_forward": [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
@@ -76,6 +78,8 @@ SIGNATURES = {
     "gn_htr_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "gn_message_backward": [_P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                             _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, C.c_long, _I, _I, _I, _I, _I, _I, _I, _P],
+    "gn_message_backward_dropout": [_P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                    _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, C.c_long, _I, _I, _I, _I, _I, _I, _I, _P],
     "gn_message_backward_groups": [_I, _I, _I, _I],
     "gn_eqff_backward_a": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "gn_eqff_backward_b": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],

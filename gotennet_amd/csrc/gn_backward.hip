@@ -284,8 +284,9 @@ __device__ __forceinline__ void msg_bwd_target_body(const MsgBwdArgs& p, float* 
         }
     }
     __syncthreads();
-    // ---- phase 2: softmax backward per head:  g_s = a g_a - (a / nrm) sum_e' a g_a
+    // ---- phase 2: softmax backward per head:  g_s = a g_a - (a_soft / nrm) sum_e' a g_a  (a_soft = a without dropout)
     {
+        const float* __restrict__ as_ = p.a_soft;
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
         for (int h = wave; h < H; h += 4) {
             float dot = 0.f;
@@ -294,7 +295,8 @@ __device__ __forceinline__ void msg_bwd_target_body(const MsgBwdArgs& p, float* 
             for (int e = e0 + lane; e < e1; e += 64) {
                 const float nrm = outdeg_ ? sqrtf((float)outdeg_[src_[e]]) * p.inv_sqrt_f : p.inv_sqrt_f;
                 const float av = a_[(size_t)e * H + h];
-                GS(e, h) = av * GS(e, h) - (av / nrm) * dot;
+                const float sv = as_ ? as_[(size_t)e * H + h] : av;
+                GS(e, h) = av * GS(e, h) - (sv / nrm) * dot;
             }
         }
     }
@@ -649,7 +651,8 @@ __device__ __forceinline__ void attn_bwd_body(const MsgBwdArgs& p, const float* 
             for (int e = e0 + lane; e < e1; e += 64) {
                 const float nrm = p.outdeg ? sqrtf((float)p.outdeg[p.src[e]]) * p.inv_sqrt_f : p.inv_sqrt_f;
                 const float av = p.a[(size_t)e * H + h];
-                GS(e, h) = av * GS(e, h) - (av / nrm) * dot;
+                const float sv = p.a_soft ? p.a_soft[(size_t)e * H + h] : av;
+                GS(e, h) = av * GS(e, h) - (sv / nrm) * dot;
             }
         }
     }
@@ -1383,14 +1386,14 @@ extern "C" int gn_message_backward_groups(int lmax_arg, int sep_dir, int sep_ten
     return (lmax >= 3 && sep_dir && sep_tensor) ? lmax - 1 : 1;
 }
 
-extern "C" int gn_message_backward(
+static int message_backward(
     const float* x, const float* v, int ldxv, const float* eproj, int lde, const float* a,
     const float* qk, int ldqk, const float* X_in, const float* rl, const float* cut, const int* outdeg,
     const float* g_h1, const float* g_X1,
     const int* rowptr, const int* src, const int* dst, const int* colptr, const int* perm,
     float* g_eproj, float* g_s, float* g_nproj, int ldn, float* g_x, float* g_v, float* g_X_out,
     float* g_rl, float* g_cut, float* ga_parts, long E,
-    int N, int F, int H, int lmax_arg, int sep_dir, int sep_tensor, int act, void* stream) {
+    int N, int F, int H, int lmax_arg, int sep_dir, int sep_tensor, int act, void* stream, const float* a_soft) {
     const int lmax = lmax_arg & 0xff;               // GN_LMAX_SLICED / GN_LMAX_MEAN / GN_LMAX_MAX may ride in the argument
     const bool amax = (lmax_arg & GN_LMAX_MAX) != 0;
     if (amax && ((lmax_arg & GN_LMAX_MEAN) || !ga_parts || !X_in)) return GN_ERR_BAD_ARG;   // "max": ga_parts = the [E, 1 + D, F] workspace
@@ -1401,7 +1404,7 @@ extern "C" int gn_message_backward(
     if (N == 0) return GN_OK;
     gn::MsgBwdArgs p{x, v, ldxv, eproj, lde, a, qk, ldqk, X_in, rl, cut, outdeg, g_h1, g_X1,
                      rowptr, src, dst, colptr, perm, g_eproj, g_s, g_nproj, ldn, g_x, g_v, g_X_out, g_rl, g_cut,
-                     N, F, H, (float)(1.0 / sqrt((double)F)), act, (lmax_arg & GN_LMAX_MEAN) ? 1 : 0, amax ? ga_parts : nullptr};
+                     N, F, H, (float)(1.0 / sqrt((double)F)), act, (lmax_arg & GN_LMAX_MEAN) ? 1 : 0, amax ? ga_parts : nullptr, a_soft};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(gn::xcd_grid(N)), block(256);
     // (F > 256: the degree-sliced kernels; g_rl / g_cut come as F / 256 partial slices, the caller sized them so)
@@ -1442,6 +1445,34 @@ extern "C" int gn_message_backward(
     }
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+
+extern "C" int gn_message_backward(
+    const float* x, const float* v, int ldxv, const float* eproj, int lde, const float* a,
+    const float* qk, int ldqk, const float* X_in, const float* rl, const float* cut, const int* outdeg,
+    const float* g_h1, const float* g_X1,
+    const int* rowptr, const int* src, const int* dst, const int* colptr, const int* perm,
+    float* g_eproj, float* g_s, float* g_nproj, int ldn, float* g_x, float* g_v, float* g_X_out,
+    float* g_rl, float* g_cut, float* ga_parts, long E,
+    int N, int F, int H, int lmax_arg, int sep_dir, int sep_tensor, int act, void* stream) {
+    return message_backward(x, v, ldxv, eproj, lde, a, qk, ldqk, X_in, rl, cut, outdeg, g_h1, g_X1, rowptr, src, dst, colptr,
+                            perm, g_eproj, g_s, g_nproj, ldn, g_x, g_v, g_X_out, g_rl, g_cut, ga_parts, E, N, F, H, lmax_arg,
+                            sep_dir, sep_tensor, act, stream, nullptr);
+}
+
+// training mode with attention dropout: `a` holds the dropped weights, `a_soft` the undropped ones
+extern "C" int gn_message_backward_dropout(
+    const float* x, const float* v, int ldxv, const float* eproj, int lde, const float* a, const float* a_soft,
+    const float* qk, int ldqk, const float* X_in, const float* rl, const float* cut, const int* outdeg,
+    const float* g_h1, const float* g_X1,
+    const int* rowptr, const int* src, const int* dst, const int* colptr, const int* perm,
+    float* g_eproj, float* g_s, float* g_nproj, int ldn, float* g_x, float* g_v, float* g_X_out,
+    float* g_rl, float* g_cut, float* ga_parts, long E,
+    int N, int F, int H, int lmax_arg, int sep_dir, int sep_tensor, int act, void* stream) {
+    if (!a_soft) return GN_ERR_BAD_ARG;
+    return message_backward(x, v, ldxv, eproj, lde, a, qk, ldqk, X_in, rl, cut, outdeg, g_h1, g_X1, rowptr, src, dst, colptr,
+                            perm, g_eproj, g_s, g_nproj, ldn, g_x, g_v, g_X_out, g_rl, g_cut, ga_parts, E, N, F, H, lmax_arg,
+                            sep_dir, sep_tensor, act, stream, a_soft);
 }
 
 extern "C" int gn_eqff_backward_a(const float* g_h, const float* g_X, const float* m, const float* Xp,

@@ -10,6 +10,7 @@
 #include "gn_common.h"
 #include "gn_tune.h"
 #include "gn_highl.h"
+#include "gn_dropout.h"
 
 namespace gn {
 
@@ -23,16 +24,26 @@ namespace gn {
 // arithmetic and its order are the same in both, so the two forms agree bit for bit.
 // ASILU: activation fixed to SiLU at compile time (the run-time switch over twelve kinds costs registers and branches).
 constexpr int ATTN_CAP = 2048;
-template <bool IN_LDS, bool ASILU>
+// DROP (training mode, gn_attn_softmax_dropout): the final write stores the weights twice -- undropped to drop.a_soft, times
+// the dropout multiplier to a[] -- and the global form keeps its scores in the a_soft rows.  A compile-time flag: the
+// instantiations without it are the ones inference launches.
+template <bool IN_LDS, bool ASILU, bool DROP = false>
 __device__ __forceinline__ void attn_softmax_body(
     const float* __restrict__ q, const float* __restrict__ k, int ldqk, const float* __restrict__ ta, int ldt,
     const int* __restrict__ src, const int* __restrict__ outdeg, int i, int e0, int e1, int F, int H, float inv_sqrt_f,
-    float* __restrict__ a, float* sc, int act) {
+    float* __restrict__ a, float* sc, int act, const AttnDrop drop = AttnDrop{}) {
+    unsigned dk0 = 0, dk1 = 0;
+    if constexpr (DROP) {
+        const unsigned long long key = (unsigned long long)drop.key[0];
+        dk0 = (unsigned)key, dk1 = (unsigned)(key >> 32);
+    }
+    auto mult = [&](size_t n) { return drop_mult(dk0, dk1, drop.layer, drop.thresh, drop.scale, drop.all, n); };
     const int lps = F >> 2, ns = 256 / lps;
     const int slot = threadIdx.x / lps, lp = threadIdx.x % lps, c0 = lp * 4;
     const int lph = lps / H;                       // lanes per head (power of two, >= 1)
     auto S = [&](int e, int h) -> float& {          // this target's score of edge e, head h
         if constexpr (IN_LDS) return sc[(e - e0) * H + h];
+        else if constexpr (DROP) return drop.a_soft[(size_t)e * H + h];
         else return a[(size_t)e * H + h];
     };
     const float4 qi = ld4(q + (size_t)i * ldqk + c0);
@@ -74,12 +85,20 @@ __device__ __forceinline__ void attn_softmax_body(
         for (int e = e0 + lane; e < e1; e += 64) {
             const float nrm = outdeg ? sqrtf((float)outdeg[src[e]]) * inv_sqrt_f : inv_sqrt_f;
             S(e, h) = S(e, h) * rsm * nrm;
+            if constexpr (DROP && !IN_LDS) a[(size_t)e * H + h] = S(e, h) * mult((size_t)e * H + h);
         }
     }
     if constexpr (IN_LDS) {
         __syncthreads();
         const int n = (e1 - e0) * H;
-        for (int idx = threadIdx.x; idx < n; idx += 256) a[(size_t)e0 * H + idx] = sc[idx];
+        for (int idx = threadIdx.x; idx < n; idx += 256) {
+            if constexpr (DROP) {
+                drop.a_soft[(size_t)e0 * H + idx] = sc[idx];
+                a[(size_t)e0 * H + idx] = sc[idx] * mult((size_t)e0 * H + idx);
+            } else {
+                a[(size_t)e0 * H + idx] = sc[idx];
+            }
+        }
     }
 }
 
@@ -100,6 +119,23 @@ __global__ __launch_bounds__(256) GN_WPE(GN_W_ATTN) void attn_softmax_kernel(
         attn_softmax_body<false, ASILU>(q, k, ldqk, ta, ldt, src, outdeg, i, e0, e1, F, H, inv_sqrt_f, a, sc, act);
 }
 
+template <bool ASILU>
+__global__ __launch_bounds__(256) void attn_softmax_drop_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, int ldqk,
+    const float* __restrict__ ta, int ldt,
+    const int* __restrict__ rowptr, const int* __restrict__ src, const int* __restrict__ outdeg,
+    int N, int F, int H, float inv_sqrt_f, float* __restrict__ a, int act_rt, const AttnDrop drop) {
+    __shared__ float sc[ATTN_CAP];
+    const int act = ASILU ? (int)GN_ACT_SILU : act_rt;
+    const int i = xcd_item(blockIdx.x, N);
+    if (i < 0) return;
+    const int e0 = rowptr[i], e1 = rowptr[i + 1];
+    if ((e1 - e0) * H <= ATTN_CAP)
+        attn_softmax_body<true, ASILU, true>(q, k, ldqk, ta, ldt, src, outdeg, i, e0, e1, F, H, inv_sqrt_f, a, sc, act, drop);
+    else
+        attn_softmax_body<false, ASILU, true>(q, k, ldqk, ta, ldt, src, outdeg, i, e0, e1, F, H, inv_sqrt_f, a, sc, act, drop);
+}
+
 // ---- one WAVE per target (F <= 256, H | 64): what ships for the default shapes.
 // Round-3 counters on the workgroup-per-target kernel above (C2: 29 us for 55 MB): VALU-bound -- 1080 VALU instructions
 // per wave, four waves per target, 20 % of the wave time issuing, the rest stalled on issue or parked at two barriers and
@@ -109,17 +145,18 @@ __global__ __launch_bounds__(256) GN_WPE(GN_W_ATTN) void attn_softmax_kernel(
 // (H | 64), so the reductions are log2(64 / H) xor-shuffles, there is no barrier anywhere, and a[] is written once,
 // coalesced.  Targets whose scores exceed the strip use their a[] rows as the strip (same code, same order).
 constexpr int ATTN_W_STRIP = 512;                   // floats per wave: 64 incoming edges at 8 heads
-template <bool IN_LDS, bool ASILU, int FC>
+// DROP: as in attn_softmax_body -- both arrays in the final write; the global strip is the target's a_soft rows.
+template <bool IN_LDS, bool ASILU, int FC, bool DROP = false>
 __device__ __forceinline__ void attn_softmax_wave_body(
     const float* __restrict__ q, const float* __restrict__ k, int ldqk, const float* __restrict__ ta, int ldt,
     const int* __restrict__ src, const int* __restrict__ outdeg, int i, int e0, int e1, int F_rt, int H, float inv_sqrt_f,
-    float* __restrict__ a, float* sc, int act) {
+    float* __restrict__ a, float* sc, int act, const AttnDrop drop = AttnDrop{}) {
     const int F = FC ? FC : F_rt;                   // FC = 256: one edge per step, every index of the walk is wave-uniform
     const int lane = threadIdx.x & 63;
     const int lps = F >> 2, ns = 64 / lps;          // lanes per edge, edges per step
     const int slot = FC == 256 ? 0 : lane / lps, lp = lane % lps, c0 = lp * 4;
     const int lph = lps / H;                        // lanes per head
-    float* const S = IN_LDS ? sc : a + (size_t)e0 * H;            // strip: S[(e - e0) * H + h]
+    float* const S = IN_LDS ? sc : (DROP ? drop.a_soft : a) + (size_t)e0 * H;   // strip: S[(e - e0) * H + h]
     const int n = (e1 - e0) * H;
     const float4 qi = ld4(q + (size_t)i * ldqk + c0);
     constexpr int U = 8;                            // steps per trip: U (index -> row) chains and U streamed rows in flight
@@ -160,9 +197,18 @@ __device__ __forceinline__ void attn_softmax_wave_body(
     const float rsm = __builtin_amdgcn_rcpf(sm + 1e-16f);
     if constexpr (!IN_LDS) __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
+    unsigned long long dkey = 0;
+    if constexpr (DROP) dkey = (unsigned long long)drop.key[0];
     for (int idx = lane; idx < n; idx += 64) {
         const float nrm = outdeg ? sqrtf((float)outdeg[src[e0 + idx / H]]) * inv_sqrt_f : inv_sqrt_f;
-        a[(size_t)e0 * H + idx] = S[idx] * rsm * nrm;
+        if constexpr (DROP) {
+            const float w = S[idx] * rsm * nrm;
+            drop.a_soft[(size_t)e0 * H + idx] = w;
+            a[(size_t)e0 * H + idx] = w * drop_mult((unsigned)dkey, (unsigned)(dkey >> 32), drop.layer, drop.thresh, drop.scale,
+                                                    drop.all, (size_t)e0 * H + idx);
+        } else {
+            a[(size_t)e0 * H + idx] = S[idx] * rsm * nrm;
+        }
     }
 }
 
@@ -186,6 +232,36 @@ __global__ __launch_bounds__(256) void attn_softmax_wave_kernel(
         attn_softmax_wave_body<true, ASILU, FC>(q, k, ldqk, ta, ldt, src, outdeg, i, e0, e1, F, H, inv_sqrt_f, a, sc, act);
     else
         attn_softmax_wave_body<false, ASILU, FC>(q, k, ldqk, ta, ldt, src, outdeg, i, e0, e1, F, H, inv_sqrt_f, a, sc, act);
+}
+
+template <bool ASILU>
+__global__ __launch_bounds__(256) void attn_softmax_drop_wave_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, int ldqk,
+    const float* __restrict__ ta, int ldt,
+    const int* __restrict__ rowptr, const int* __restrict__ src, const int* __restrict__ outdeg,
+    int N, int F, int H, float inv_sqrt_f, float* __restrict__ a, int act_rt, const AttnDrop drop) {
+    __shared__ float strips[4 * ATTN_W_STRIP];
+    const int act = ASILU ? (int)GN_ACT_SILU : act_rt;
+    const int grp = xcd_item(blockIdx.x, (N + 3) >> 2);
+    if (grp < 0) return;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i = 4 * grp + wave;
+    if (i >= N) return;
+    const int e0 = rowptr[i], e1 = rowptr[i + 1];
+    if (e1 == e0) return;
+    float* sc = strips + wave * ATTN_W_STRIP;
+    if ((e1 - e0) * H <= ATTN_W_STRIP)
+        attn_softmax_wave_body<true, ASILU, 0, true>(q, k, ldqk, ta, ldt, src, outdeg, i, e0, e1, F, H, inv_sqrt_f, a, sc, act, drop);
+    else
+        attn_softmax_wave_body<false, ASILU, 0, true>(q, k, ldqk, ta, ldt, src, outdeg, i, e0, e1, F, H, inv_sqrt_f, a, sc, act, drop);
+}
+
+// the [E,H] multipliers alone (what a test or a user needs to reproduce a step)
+__global__ __launch_bounds__(256) void attn_dropout_mask_kernel(const long long* __restrict__ key, unsigned layer, unsigned thresh,
+                                                                float scale, int all, unsigned long long n, float* __restrict__ m) {
+    const unsigned long long k = (unsigned long long)key[0];
+    for (unsigned long long idx = (unsigned long long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (unsigned long long)gridDim.x * 256)
+        m[idx] = drop_mult((unsigned)k, (unsigned)(k >> 32), layer, thresh, scale, all, idx);
 }
 
 // ------------------------------------------------------------------ K6 message + aggregate (lmax <= 2: one launch)
@@ -527,6 +603,59 @@ extern "C" int gn_attn_softmax(const float* q, const float* k, int ldqk, const f
     else
         hipLaunchKernelGGL(gn::attn_softmax_kernel<false>, dim3(gn::xcd_grid(N)), dim3(256), 0, (hipStream_t)stream,
                            q, k, ldqk, t_attn, ldt, rowptr, src, outdeg, N, F, H, inv_sqrt_f, a, act);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+// p -> (threshold, multiplier, "drops everything"); false for a p that is no probability
+static bool drop_params(double p, unsigned& thresh, float& scale, int& all) {
+    if (!(p >= 0.0)) return false;
+    all = p >= 1.0 ? 1 : 0;
+    thresh = all ? 0xffffffffu : (unsigned)floor(p * 4294967296.0);
+    scale = all ? 0.f : (float)(1.0 / (1.0 - p));
+    return true;
+}
+
+extern "C" int gn_attn_softmax_dropout(const float* q, const float* k, int ldqk, const float* t_attn, int ldt,
+                                       const int* rowptr, const int* src, const int* outdeg,
+                                       int N, int F, int H, float* a_soft, float* a, const long long* key, int layer, double p,
+                                       int act, void* stream) {
+    gn::AttnDrop d{a_soft, key, (unsigned)layer, 0u, 0.f, 0};
+    if (!feature_dim_ok(F) || N < 0 || H <= 0 || !gn::is_pow2(H) || (F / 4) % H || (F / 4) / H > 64 ||
+        (ldqk & 3) || (ldt & 3) || act < 0 || act >= GN_ACT_COUNT || !key || !a_soft || a_soft == a || layer < 0 ||
+        !drop_params(p, d.thresh, d.scale, d.all))
+        return GN_ERR_BAD_ARG;
+    if (N == 0) return GN_OK;
+    const float inv_sqrt_f = (float)(1.0 / sqrt((double)F));
+    if (GN_ATTN_WAVE && F <= 256 && H <= 64) {        // the same choice of form as gn_attn_softmax
+        const dim3 grid(gn::xcd_grid((N + 3) / 4)), block(256);
+        if (act == GN_ACT_SILU)
+            hipLaunchKernelGGL(gn::attn_softmax_drop_wave_kernel<true>, grid, block, 0, (hipStream_t)stream,
+                               q, k, ldqk, t_attn, ldt, rowptr, src, outdeg, N, F, H, inv_sqrt_f, a, act, d);
+        else
+            hipLaunchKernelGGL(gn::attn_softmax_drop_wave_kernel<false>, grid, block, 0, (hipStream_t)stream,
+                               q, k, ldqk, t_attn, ldt, rowptr, src, outdeg, N, F, H, inv_sqrt_f, a, act, d);
+        GN_LAUNCH_CHECK();
+        return GN_OK;
+    }
+    if (act == GN_ACT_SILU)
+        hipLaunchKernelGGL(gn::attn_softmax_drop_kernel<true>, dim3(gn::xcd_grid(N)), dim3(256), 0, (hipStream_t)stream,
+                           q, k, ldqk, t_attn, ldt, rowptr, src, outdeg, N, F, H, inv_sqrt_f, a, act, d);
+    else
+        hipLaunchKernelGGL(gn::attn_softmax_drop_kernel<false>, dim3(gn::xcd_grid(N)), dim3(256), 0, (hipStream_t)stream,
+                           q, k, ldqk, t_attn, ldt, rowptr, src, outdeg, N, F, H, inv_sqrt_f, a, act, d);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_attn_dropout_mask(const long long* key, int layer, double p, long E, int H, float* m_out, void* stream) {
+    unsigned thresh; float scale; int all;
+    if (!key || layer < 0 || E < 0 || H <= 0 || !drop_params(p, thresh, scale, all)) return GN_ERR_BAD_ARG;
+    const unsigned long long n = (unsigned long long)E * (unsigned long long)H;
+    if (n == 0) return GN_OK;
+    const unsigned long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(gn::attn_dropout_mask_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
+                       (hipStream_t)stream, key, (unsigned)layer, thresh, scale, all, n, m_out);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }

@@ -49,6 +49,9 @@ struct MsgBwdArgs {
     const float* g_edge;                               // aggr = "max" (degree-sliced kernels only): [E, 1 + D, F] upstream gradient of
                                                        // every MESSAGE (row 0: scalar, rows 1..D: tensor), routed to the arg-max
                                                        // edges by hl_max_route_kernel; NULL: the per-target rows g_h1 / g_X1
+    const float* a_soft;                               // attention dropout (gn_message_backward_dropout): [E, H] the UNDROPPED weights,
+                                                       // `a` then holds the dropped ones; read only for the (a / nrm) prefactor of the
+                                                       // softmax backward.  NULL: same as `a`
 };
 
 // gamma_w (gotennet.py:285-291): 0 identity, 1 nn.Sigmoid ("gated"), 2 nn.Tanh ("gatedt"), 3 nn.SiLU ("act")

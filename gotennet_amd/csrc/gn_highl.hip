@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void hl_msg_bwd_target_kernel(const MsgBwdArgs
         if (wide) __syncthreads();
     }
     __syncthreads();
-    // softmax backward per head:  g_s = a g_a - (a / nrm) sum_e' a g_a
+    // softmax backward per head:  g_s = a g_a - (a_soft / nrm) sum_e' a g_a  (a_soft = a without dropout)
     {
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
         for (int h = wave; h < H; h += 4) {
@@ -280,7 +280,8 @@ __global__ __launch_bounds__(256) void hl_msg_bwd_target_kernel(const MsgBwdArgs
             for (int e = e0 + lane; e < e1; e += 64) {
                 const float nrm = p.outdeg ? sqrtf((float)p.outdeg[p.src[e]]) * p.inv_sqrt_f : p.inv_sqrt_f;
                 const float av = p.a[(size_t)e * H + h];
-                p.g_s[(size_t)e * H + h] = av * p.g_s[(size_t)e * H + h] - (av / nrm) * dot;
+                const float sv = p.a_soft ? p.a_soft[(size_t)e * H + h] : av;
+                p.g_s[(size_t)e * H + h] = av * p.g_s[(size_t)e * H + h] - (sv / nrm) * dot;
             }
         }
     }

@@ -128,6 +128,9 @@ class Config:
     fuse_eqff: Optional[bool] = None   # the node-local EQFF chain as ONE kernel each way where covered (eqff_fused_ok).  None =
                               # auto: on for systems of at most EQFF_FUSED_MAX_ATOMS atoms (launch-bound: -17 % on a one-molecule
                               # step, -2 % at 32 molecules), off above (a wash at the 128-molecule batch)
+    attn_p: float = 0.0       # attention-dropout probability of THIS call (gotennet.py:513): > 0 only in the configuration a
+                              # training-mode forward builds for itself (``GotenNet._dropout_call``); the module's own
+                              # ``config()`` -- what the inference tools take -- always says 0
 
     @property
     def Fe(self) -> int:
@@ -293,9 +296,11 @@ class _Call:
     """What ONE forward / backward / stand-alone layer call binds, evaluated once (a one-molecule eager step is host-bound):
     the projection launchers with the model's arithmetic and activation kind (``cfg.gemm_mode``, ``cfg.act``), the
     configuration, the graph, the stream, the sizes, the degree blocks and the gate columns ``cols[first]``."""
-    __slots__ = ("mode", "act", "cfg", "g", "st", "N", "E", "F", "D", "Fe", "lde", "blocks", "cols")
+    __slots__ = ("mode", "act", "cfg", "g", "st", "N", "E", "F", "D", "Fe", "lde", "blocks", "cols", "key")
 
-    def __init__(self, cfg: "Config", g: Optional["Graph"] = None, explicit_blocks: bool = False):
+    def __init__(self, cfg: "Config", g: Optional["Graph"] = None, explicit_blocks: bool = False,
+                 key: Optional[torch.Tensor] = None):
+        self.key = key                             # attention dropout: this call's key, an int64 [2] device tensor (or None)
         self.mode, self.act, self.cfg, self.g, self.st = resolve_mode(cfg.gemm_mode), cfg.act, cfg, g, _stream()
         self.F, self.D, self.Fe, self.lde = cfg.F, cfg.D, cfg.Fe, (1 + cfg.M) * cfg.F
         # columns of (the edge projection [W_re; W_rs], gamma_s.1 / gamma_v.1) a layer computes: attention (edge only), scalar,
@@ -402,6 +407,7 @@ class LayerTape:
     h_in: torch.Tensor = None; X_in: torch.Tensor = None; t_in: torch.Tensor = None
     nproj: torch.Tensor = None; xs: torch.Tensor = None; vs: torch.Tensor = None
     eproj: torch.Tensor = None; attn: torch.Tensor = None
+    attn_soft: torch.Tensor = None                 # attention dropout: the undropped weights (``attn`` holds the dropped ones)
     EQ: torch.Tensor = None; EK: torch.Tensor = None; w: torch.Tensor = None; pre_t: torch.Tensor = None
     w_raw: torch.Tensor = None; h_raw: torch.Tensor = None; X_raw: torch.Tensor = None
     upd: dict = None                               # intermediates of the composed edge update
@@ -416,6 +422,25 @@ class Tape:
     feat: torch.Tensor = None; y_pre: torch.Tensor = None; h0: torch.Tensor = None
     ctx0: torch.Tensor = None; y: torch.Tensor = None           # parameter gradients only: inputs of W_nrd_nru.{0,1}
     layers: List[LayerTape] = field(default_factory=list)
+    key: torch.Tensor = None                                     # attention dropout: the key of the forward that wrote the tape
+
+
+def draw_dropout_key(device, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """One attention-dropout key: int64 [2] = (seed, reserved) drawn ON the device with one ``torch.randint`` launch, from
+    ``generator`` or the device's default generator (so ``torch.manual_seed`` makes a run reproducible).  No host read."""
+    return torch.randint(0, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device, generator=generator)
+
+
+def attention_dropout_mask(key: torch.Tensor, layer: int, E: int, H: int, p: float) -> torch.Tensor:
+    """The [E, H] multipliers (0 or 1 / (1 - p)) that layer ``layer`` of the call with ``key`` applied to its attention
+    weights: the mask function of include/gotennet_hip.h, evaluated by gn_attn_dropout_mask.  Rows are the edges in the
+    target-major order the engine runs on (a target-sorted edge list is in that order already)."""
+    if not key.is_cuda or key.dtype != torch.int64 or key.numel() < 2 or not key.is_contiguous():
+        raise ValueError("key: a contiguous int64 device tensor of two values (GotenNet.last_dropout_key)")
+    m = torch.empty((E, H), dtype=torch.float32, device=key.device)
+    with torch.cuda.device(key.device):
+        call("gn_attn_dropout_mask", ptr(key), int(layer), float(p), E, H, ptr(m), _stream())
+    return m
 
 
 def check_backward_supported(cfg: Config) -> None:
@@ -527,6 +552,8 @@ def _layer_buffers(cfg: Config, N: int, E: int, new, last: bool, save: bool, pgr
     F_, D, M, Fe = cfg.F, cfg.D, cfg.M, cfg.Fe
     lt = LayerTape(xs=new(N, M * F_), vs=new(N, M * F_), eproj=new(E, (1 + M) * F_), attn=new(E, cfg.H),
                    Xp=new(N, D, F_), ctx=new(N, 2 * F_), mm=new(N, 2 * F_))
+    if cfg.attn_p > 0:
+        lt.attn_soft = new(E, cfg.H)
     if save:
         lt.nproj, lt.pre_g1 = new(N, 4 * F_), new(N, F_)
     if not last:
@@ -539,10 +566,12 @@ def _layer_buffers(cfg: Config, N: int, E: int, new, last: bool, save: bool, pgr
     return lt, new(N, F_), new(N, D, F_), (None if last else new(E, F_))
 
 
-def _gata_forward(p: _Call, lw: LayerWeights, lt: LayerTape, nact, h, X, t, h2, X2):
+def _gata_forward(p: _Call, lw: LayerWeights, lt: LayerTape, nact, h, X, t, h2, X2, li: int = 0):
     """GATA projections (gotennet.py:400-407) and message stage (452-559, 613-640, 426-427: scores + segment softmax,
     message, aggregate, residual) of one layer: writes h2, X2, ``nact`` and lt.xs, vs, eproj, attn -- and the pre-activation
-    copy lt.nproj, where it is not None.  ``lt.first``: X is the zero tensor, no tensor-gate blocks."""
+    copy lt.nproj, where it is not None.  ``lt.first``: X is the zero tensor, no tensor-gate blocks.  With attention
+    dropout (``cfg.attn_p > 0``) lt.attn holds the dropped weights of layer ``li`` under the call's key, lt.attn_soft the
+    undropped ones."""
     cfg, g, st, F_, lde, N, E, first = p.cfg, p.g, p.st, p.F, p.lde, p.N, p.E, lt.first
     H, M, xs, vs, eproj, attn = cfg.H, cfg.M, lt.xs, lt.vs, lt.eproj, lt.attn
     ne, nv = p.cols[first]
@@ -557,8 +586,13 @@ def _gata_forward(p: _Call, lw: LayerWeights, lt: LayerTape, nact, h, X, t, h2, 
              dict(A=nact, lda=4 * F_, W=_rows(lw, "Wv2", nv) if first else lw.Wv2, bias=lw.bv2, C=vs, ldc=M * F_, rows=N,
                   nout=nv, K=F_, a_off=3 * F_)])
     # q | k are columns [0, 2F) of nact; t_attn (pre-activation) columns [0, F) of eproj, t_filter the rest
-    call("gn_attn_softmax", ptr(nact), nact.data_ptr() + 4 * F_, 4 * F_, ptr(eproj), lde,
-         ptr(g.rowptr), ptr(g.src), ptr(g.outdeg), N, F_, H, ptr(attn), cfg.act, st)
+    if cfg.attn_p > 0:
+        call("gn_attn_softmax_dropout", ptr(nact), nact.data_ptr() + 4 * F_, 4 * F_, ptr(eproj), lde,
+             ptr(g.rowptr), ptr(g.src), ptr(g.outdeg), N, F_, H, ptr(lt.attn_soft), ptr(attn), ptr(p.key), li,
+             float(cfg.attn_p), cfg.act, st)
+    else:
+        call("gn_attn_softmax", ptr(nact), nact.data_ptr() + 4 * F_, 4 * F_, ptr(eproj), lde,
+             ptr(g.rowptr), ptr(g.src), ptr(g.outdeg), N, F_, H, ptr(attn), cfg.act, st)
     call("gn_message_aggregate", ptr(xs), ptr(vs), M * F_, eproj.data_ptr() + 4 * F_, lde,
          ptr(attn), ptr(g.rl), ptr(g.cut), ptr(g.rowptr), ptr(g.src), ptr(h), None if first else ptr(X), ptr(h2), ptr(X2),
          N, F_, H, cfg.lmax_arg_msg, int(cfg.sep_dir), int(cfg.sep_tensor), st)
@@ -604,10 +638,11 @@ def _eqff_htr_forward(p: _Call, lw: LayerWeights, lt: LayerTape, g1act, h, X, t,
 
 
 def forward(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, save: bool = False,
-            trace: Optional[list] = None, pgrads: bool = False):
+            trace: Optional[list] = None, pgrads: bool = False, key: Optional[torch.Tensor] = None):
     """-> (h [N,F], X [N,D,F], tape or None).  ``save`` keeps what ``backward`` needs; ``pgrads`` (with ``save``, and a
     ``param_grad_config``) also keeps the inputs of every projection for the parameter gradients;
-    ``trace`` (tests only) collects per-layer clones of (h, X, t)."""
+    ``trace`` (tests only) collects per-layer clones of (h, X, t).  ``key``: the call's attention-dropout key
+    (``draw_dropout_key``), required when ``cfg.attn_p > 0``; the tape keeps it next to both attention arrays."""
     F_, D, N, E = cfg.F, cfg.D, g.N, g.E
     if save:
         check_backward_supported(cfg)               # before any launch: a saving forward is only run for a backward
@@ -615,10 +650,12 @@ def forward(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, save: b
         check_param_grads_supported(cfg)
         if not save or cfg.fuse_eqff is not False:
             raise ValueError("internal: a parameter-gradient forward saves its tape and runs the un-fused EQFF chain")
-    p = _Call(cfg, g)
+    if cfg.attn_p > 0 and key is None:
+        raise ValueError("internal: a forward with attention dropout needs the call's key (draw_dropout_key)")
+    p = _Call(cfg, g, key=key)
     f32 = dict(dtype=torch.float32, device=z32.device)
     new = lambda *shape: torch.empty(shape, **f32)
-    tape = Tape() if save else None
+    tape = Tape(key=key) if save else None
     h, t = _init_forward(p, pw, z32, new, tape, pgrads)
     # gotennet.py:992: X starts as the zero tensor.  Where the first interaction runs the zero-X_in kernels nothing ever reads
     # it (message stage and message backward get a null X_in): no fill launch
@@ -644,7 +681,7 @@ def forward(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, save: b
             if pgrads:
                 nact, g1act = lt.nact, lt.g1act
         lt.first = first
-        _gata_forward(p, lw, lt, nact, h, X, t, h2, X2)
+        _gata_forward(p, lw, lt, nact, h, X, t, h2, X2, li)
         h, h2 = h2, h
         X, X2 = X2, X
         if pgrads:
@@ -660,18 +697,23 @@ def forward(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, save: b
     return h, X, tape
 
 
-def gata_layer(cfg: Config, lw: LayerWeights, g: "Graph", h: torch.Tensor, X: torch.Tensor, t: torch.Tensor):
-    """ONE GATA layer (gotennet.py:366-450) on its own, inference only: what ``GATA.forward`` of the mirror module runs
+def gata_layer(cfg: Config, lw: LayerWeights, g: "Graph", h: torch.Tensor, X: torch.Tensor, t: torch.Tensor,
+               key: Optional[torch.Tensor] = None):
+    """ONE GATA layer (gotennet.py:366-450) on its own, no backward: what ``GATA.forward`` of the mirror module runs
     when a caller composes layers directly.  Same kernels as ``forward`` (which additionally fuses the neighbouring EQFF
-    launches into the grouped GEMMs).  ``g`` carries the CSR view, rl and the cosine cutoff.  -> (h', X', t')."""
+    launches into the grouped GEMMs).  ``g`` carries the CSR view, rl and the cosine cutoff.  With ``cfg.attn_p > 0``
+    (a module in training mode) attention dropout is applied as layer 0 of ``key``.  -> (h', X', t')."""
     F_, D, M, Fe, N, E = cfg.F, cfg.D, cfg.M, cfg.Fe, g.N, g.E
-    p = _Call(cfg, g)
+    if cfg.attn_p > 0 and key is None:
+        raise ValueError("internal: a layer with attention dropout needs the call's key (draw_dropout_key)")
+    p = _Call(cfg, g, key=key)
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=h.device)
     if cfg.layernorm:
         h = _norm_h(lw, h)
     if cfg.steerable_norm:
         X = _norm_X(lw, X, cfg.lmax)
-    lt = LayerTape(xs=new(N, M * F_), vs=new(N, M * F_), eproj=new(E, p.lde), attn=new(E, cfg.H))
+    lt = LayerTape(xs=new(N, M * F_), vs=new(N, M * F_), eproj=new(E, p.lde), attn=new(E, cfg.H),
+                   attn_soft=new(E, cfg.H) if cfg.attn_p > 0 else None)
     h2, X2 = new(N, F_), new(N, D, F_)
     _gata_forward(p, lw, lt, new(N, 4 * F_), h, X, t, h2, X2)
     if lw.Wt is None:
@@ -999,7 +1041,10 @@ def _gata_backward(p: _Call, lw: LayerWeights, lt: LayerTape, wb: _BackwardWork,
         raise RuntimeError("internal: the tape of a general-path layer holds no X_in")
     if first and G > 1:                            # one launch instead of G degree groups: one g_cut slice is written
         wb.g_cut_parts[wb.msg_cut * li + 1:wb.msg_cut * li + G].zero_()   # (never with wide slots: zero_X_in excludes them)
-    call("gn_message_backward", ptr(lt.xs), ptr(lt.vs), M * F_, ptr(lt.eproj), lde, ptr(lt.attn),
+    # (a layer that ran with attention dropout: lt.attn = the dropped weights, lt.attn_soft the softmax's own)
+    drop = lt.attn_soft is not None
+    call("gn_message_backward_dropout" if drop else "gn_message_backward", ptr(lt.xs), ptr(lt.vs), M * F_, ptr(lt.eproj),
+         lde, ptr(lt.attn), *((ptr(lt.attn_soft),) if drop else ()),
          ptr(lt.nproj), 4 * F_, None if first else ptr(lt.X_in), ptr(g.rl), ptr(g.cut), ptr(g.outdeg),
          ptr(wb.gh1), ptr(wb.gX1), ptr(g.rowptr), ptr(g.src), ptr(g.tgt_by_src), ptr(wb.colptr), ptr(wb.perm),
          ptr(wb.g_eproj), ptr(wb.g_s), ptr(wb.g_nproj), 4 * F_, ptr(wb.g_x), ptr(wb.g_v), None if first else ptr(wb.gX2),

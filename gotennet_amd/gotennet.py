@@ -9,6 +9,7 @@ Calling ``forward`` on CPU tensors, or without the built library, raises.
 """
 from __future__ import annotations
 
+import dataclasses
 from functools import partial
 from typing import Callable, Mapping, Optional, Tuple, Union
 
@@ -31,8 +32,9 @@ class _RepresentationFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, edge_diff, edge_vec, net, z32, edge_index):
         cfg, pw = net.config(), net.packed_weights()
+        cfg, key = net._dropout_call(cfg, z32.device)
         g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff.detach(), edge_vec.detach())
-        h, X, tape = engine.forward(cfg, pw, z32, g, save=True)
+        h, X, tape = engine.forward(cfg, pw, z32, g, save=True, key=key)
         ctx.state = (cfg, pw, z32, g, tape)
         return h, X
 
@@ -52,9 +54,10 @@ class _RepresentationPosFn(torch.autograd.Function):
     def forward(ctx, pos, net, z32, batch):
         from .graph import distance
         cfg, pw = net.config(), net.packed_weights()
+        cfg, key = net._dropout_call(cfg, z32.device)
         edge_index, edge_diff, edge_vec = distance(pos.detach(), batch, net.cutoff, net.max_num_neighbors)
         g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff, edge_vec)
-        h, X, tape = engine.forward(cfg, pw, z32, g, save=True)
+        h, X, tape = engine.forward(cfg, pw, z32, g, save=True, key=key)
         ctx.state = (cfg, pw, z32, g, tape)
         return h, X
 
@@ -106,8 +109,9 @@ class positions_only:
 
 def _param_forward(ctx, net, z32, g, params):
     ctx.gn_param_fn, ctx.gn_positions_only = True, False
-    cfg, pw = ctx.cfg, ctx.pw
-    h, X, tape = engine.forward(cfg, pw, z32, g, save=True, pgrads=True)
+    pw = ctx.pw
+    cfg, key = net._dropout_call(ctx.cfg, z32.device)      # training mode: this call's mask; the tape keeps both attention arrays
+    h, X, tape = engine.forward(cfg, pw, z32, g, save=True, pgrads=True, key=key)
     ctx.state = (cfg, pw, z32, g, tape, net, params)
     return h, X
 
@@ -265,8 +269,10 @@ def _require_cuda(t: Tensor, what: str):
 
 class GATA(_LayerPackCache, nn.Module):
     """One GATA layer (reference gotennet.py:78-657): parameters under the reference's names, and ``forward`` with the
-    reference's signature driving the HIP kernels (inference only; inside ``GotenNet`` the stack driver sequences the
-    same kernels with the neighbouring EQFF launches fused in)."""
+    reference's signature driving the HIP kernels (no backward; inside ``GotenNet`` the stack driver sequences the
+    same kernels with the neighbouring EQFF launches fused in).  In ``train()`` mode with ``dropout > 0`` the attention
+    weights are dropped as layer 0 of a key drawn for the call (``dropout_generator`` / ``last_dropout_key``, as on
+    ``GotenNet``)."""
 
     def __init__(self, n_atom_basis: int, activation: Callable, weight_init=nn.init.xavier_uniform_,
                  bias_init=nn.init.zeros_, aggr: str = "add", epsilon: float = 1e-7, layer_norm: str = "",
@@ -310,6 +316,8 @@ class GATA(_LayerPackCache, nn.Module):
         self.last_layer, self.edge_updates, self.scale_edge = last_layer, edge_updates, scale_edge
         self.sep_htr, self.sep_dir, self.sep_tensor = sep_htr, sep_dir, sep_tensor
         self.dropout, self.epsilon, self.cutoff = dropout, epsilon, cutoff
+        self.dropout_generator: Optional[torch.Generator] = None   # None: the device's default generator
+        self.last_dropout_key: Optional[Tensor] = None
         self.act_kind = activation_kind(activation)
         multiplier = 3 + (lmax - 1 if sep_dir else 0) + (lmax - 1 if sep_tensor else 0)
         self.multiplier = multiplier
@@ -396,8 +404,6 @@ class GATA(_LayerPackCache, nn.Module):
         must BE that quantity (checked on the device, ``ValueError`` otherwise: another normalisation has no kernel).
         Any edge order.  No edges: the (optionally normalised) inputs come back unchanged."""
         _require_cuda(h, "GATA")
-        if self.training and self.dropout > 0:
-            raise NotImplementedError("attention dropout (training mode) is not on the accelerated path; call .eval()")
         if embed.needs_embedding(self.n_atom_basis):
             raise NotImplementedError(f"n_atom_basis={self.n_atom_basis}: a stand-alone GATA layer needs a power-of-two width (the slot kernels "
                                       "tile an edge row over F/4 lanes); inside GotenNet such a model runs embedded in the next one")
@@ -427,10 +433,14 @@ class GATA(_LayerPackCache, nn.Module):
                 order = torch.sort(edge_index[1], stable=True).indices
                 edge_index, rl, r, t2 = edge_index[:, order].contiguous(), rl[order].contiguous(), r[order].contiguous(), \
                     t2[order].contiguous()
+        key = None
+        if self.training and self.dropout > 0:      # gotennet.py:513; the mask's rows are the target-sorted edges
+            cfg = dataclasses.replace(cfg, attn_p=float(self.dropout))
+            key = self.last_dropout_key = engine.draw_dropout_key(h.device, self.dropout_generator)
         g = engine.Graph(cfg, None, N, edge_index)
         g.rl = rl
         engine.call("gn_cosine_cutoff", engine.ptr(r), E, float(self.cutoff), engine.ptr(g.cut), engine._stream())
-        ho, Xo, to = engine.gata_layer(cfg, lw, g, h2, X2, t2)
+        ho, Xo, to = engine.gata_layer(cfg, lw, g, h2, X2, t2, key=key)
         if order is not None and to is not t2:
             inv = torch.empty_like(order)
             inv[order] = torch.arange(E, device=order.device)
@@ -495,8 +505,14 @@ class GotenNet(nn.Module):
 
     ``forward(atomic_numbers, edge_index, edge_diff, edge_vec) -> (h [N,F], X [N,D,F])``.
     Differences from the reference, by design: inputs are left untouched (the
-    reference normalises ``edge_vec`` in place, 978-980); inference only (attention
-    dropout is inactive, as in ``eval()``); fp32; runs on a ROCm device only.
+    reference normalises ``edge_vec`` in place, 978-980); fp32; runs on a ROCm device only.
+
+    Attention dropout (``attn_dropout > 0``) is active in ``train()`` mode on every route of ``forward`` -- plain, the
+    force autograd Functions and the parameter-gradient Functions -- and inactive in ``eval()``.  Each forward call draws
+    one key on the device (from ``dropout_generator`` if set, else the device's default generator: ``torch.manual_seed``
+    makes a run reproducible); its backward reuses the arrays that forward wrote.  ``last_dropout_key`` is the last
+    call's key (an int64 [2] device tensor; ``attention_dropout_mask`` rebuilds any layer's mask from it).  It is
+    per MODULE, not per thread: with several threads calling one module, read it under the caller's own lock.
     """
 
     def __init__(self, n_atom_basis: int = 128, n_interactions: int = 8,
@@ -565,6 +581,10 @@ class GotenNet(nn.Module):
         #: grad (first order: a loss on energies and / or (h, X); engine.check_param_grads_supported lists what is refused)
         self.parameter_grads = False
         self._warned_inference_only = False
+        #: attention dropout: the generator the per-call key is drawn from (None: the device's default generator), and the
+        #: key of the last training-mode forward (per module, not per thread)
+        self.dropout_generator: Optional[torch.Generator] = None
+        self.last_dropout_key: Optional[Tensor] = None
 
     # ------------------------------------------------------------------ parameters
     def reset_parameters(self):
@@ -716,8 +736,15 @@ class GotenNet(nn.Module):
             raise ValueError("edge_diff must be 1-D [E] (reference layers.py:745 unsqueezes it)")
         if edge_vec.shape != (E, 3):
             raise ValueError("edge_vec must be [E, 3]")
-        if self.training and self.attn_dropout > 0:
-            raise NotImplementedError("attention dropout (training mode) is not on the accelerated path; call .eval()")
+
+    def _dropout_call(self, cfg: engine.Config, device):
+        """-> (the configuration of THIS forward call, its attention-dropout key or None).  Training mode with
+        ``attn_dropout > 0``: one key drawn on the device (one ``torch.randint`` launch, no host read), kept in
+        ``last_dropout_key``.  Called once per forward call, by whichever route runs it."""
+        if not (self.training and self.attn_dropout > 0):
+            return cfg, None
+        key = self.last_dropout_key = engine.draw_dropout_key(device, self.dropout_generator)
+        return dataclasses.replace(cfg, attn_p=float(self.attn_dropout)), key
 
     def _param_path(self) -> Optional[list]:
         """The parameters, when this call trains them (``parameter_grads``, grad mode on, one of them requires grad)."""
@@ -766,8 +793,9 @@ class GotenNet(nn.Module):
         if torch.is_grad_enabled() and (edge_vec.requires_grad or edge_diff.requires_grad):
             return _RepresentationFn.apply(edge_diff.contiguous(), edge_vec.contiguous(), self, z32, edge_index)
         with torch.no_grad():
+            cfg, key = self._dropout_call(cfg, z32.device)
             g = engine.Graph(cfg, pw, N, edge_index, edge_diff, edge_vec)
-            h, X, _ = engine.forward(cfg, pw, z32, g, trace=_trace)
+            h, X, _ = engine.forward(cfg, pw, z32, g, trace=_trace, key=key)
             return h, X
 
 

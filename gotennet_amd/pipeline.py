@@ -19,7 +19,9 @@ class EnergyForces:
     one host sync per call) and stable-sort it by target when needed -- energies and forces are per molecule / per atom,
     so the order of the edge list never shows in the result; the ``batch`` vector must be non-decreasing (molecules
     contiguous) and is checked too.  Callers that pass radius-graph output
-    (``gotennet_amd.graph.distance``: target-major by construction) switch it off and stay sync-free."""
+    (``gotennet_amd.graph.distance``: target-major by construction) switch it off and stay sync-free.
+
+    An inference tool: attention dropout is never applied, whatever the representation's ``training`` flag says."""
 
     def __init__(self, representation: GotenNet, head: Atomwise, check_edges: bool = True, cache_topology: bool = True,
                  replay: bool = False, replay_after: int = 2):
@@ -194,7 +196,9 @@ class InFlight:
         reallocation its inputs right after the call returns (the normal data-loader loop);
       * the tensors a call returns were allocated on the lane's stream; the object keeps a reference to them until the next
         ``wait()``, which marks them as used on the stream that waits -- read results only after ``wait()``, on that stream;
-      * a weight update (a stale pack) makes the call wait for ALL lanes before the old pack's operands are freed."""
+      * a weight update (a stale pack) makes the call wait for ALL lanes before the old pack's operands are freed.
+
+    An inference tool, like the ``EnergyForces`` lanes it feeds: attention dropout is never applied."""
 
     def __init__(self, representation: GotenNet, head: Atomwise, lanes: int = 2, **kw):
         dev = next(representation.parameters()).device
@@ -286,6 +290,8 @@ class CapturedStep:
 
         step = CapturedStep(EnergyForces(rep, head), z, edge_index, batch, n_mol)
         energy, forces = step(pos)          # views of static output buffers: copy them to keep them
+
+    An inference tool: attention dropout is never applied (the recorded step is ``EnergyForces``' own).
     """
 
     def __init__(self, ef: EnergyForces, z: torch.Tensor, edge_index: torch.Tensor, batch: torch.Tensor, n_mol: int,

@@ -38,7 +38,7 @@ extern "C" {
 
 #define GN_OK 0
 #define GN_ERR_BAD_ARG 10001     /* shape/flag combination the kernels do not implement */
-#define GN_ABI_VERSION 10
+#define GN_ABI_VERSION 11
 /* OR-ed into the `lmax` ARGUMENT of gn_message_aggregate, gn_message_backward(_groups), gn_htr_edge and
  * gn_htr_backward: run this call on the degree-sliced kernel family at lmax <= 4 as well (the family that serves
  * lmax 5..8).  An explicit per-call request -- the library reads no environment variable and keeps no switch; every
@@ -235,6 +235,26 @@ int gn_attn_softmax(const float* q, const float* k, int ldqk, const float* t_att
                     const int* rowptr, const int* src, const int* outdeg,
                     int N, int F, int H, float* a, int act /* GN_ACT_*: t_attn = act(.) */, void* stream);
 
+/* ---- attention dropout (training mode; reference gotennet.py:513, F.dropout on the attention weights) ----------
+ * The mask is a pure, counter-based function of (key, layer, e, h): nothing is stored, the forward and whoever wants to
+ * reproduce a step evaluate the same function.  For element n = e * H + h (a 64-bit count; e = the edge's index in the
+ * TARGET-MAJOR order the kernels run on, i.e. the CSR edge id):
+ *     word = output word 0 of Philox4x32-10 with counter (lo32(n), hi32(n), layer, 0) and key (lo32(key[0]), hi32(key[0]))
+ *     m[e,h] = word >= floor(p * 2^32) ? 1 / (1 - p) : 0          (1 / (1 - p) in double, rounded once to fp32)
+ * p >= 1 drops everything (m = 0, as torch does); p = 0 keeps everything with m = 1; p < 0 or NaN: GN_ERR_BAD_ARG.
+ * `key` is a DEVICE pointer to two int64 values {seed, reserved (ignored)}: the kernels read it on the device, no value
+ * crosses to the host, and a captured launch replays with whatever the buffer then holds.
+ *
+ * gn_attn_softmax_dropout: gn_attn_softmax that writes a_soft [E,H] = the weights above (softmax * norm) AND
+ * a [E,H] = a_soft * m in the same final pass (a_soft != a).  Everything downstream of the softmax (gn_message_aggregate,
+ * the message backward) takes `a`; only the softmax backward also reads a_soft (gn_message_backward_dropout). */
+int gn_attn_softmax_dropout(const float* q, const float* k, int ldqk, const float* t_attn, int ldt,
+                            const int* rowptr, const int* src, const int* outdeg,
+                            int N, int F, int H, float* a_soft, float* a, const long long* key, int layer, double p,
+                            int act, void* stream);
+/* The multipliers m [E,H] alone. */
+int gn_attn_dropout_mask(const long long* key, int layer, double p, long E, int H, float* m_out, void* stream);
+
 /* Message + segmented reduction + residual (gotennet.py:516-559, 613-640, 426-427):
  *   o[c]   = t_filter[e,c] * x[j,c] * cut[e] + a[e, c / (M F / H)] * v[j,c],  c in [0, M F)
  *   h_out[i]     = h_in[i] + sum_e o[0:F]
@@ -322,6 +342,17 @@ int gn_message_backward(const float* x, const float* v, int ldxv, const float* e
                         float* g_eproj, float* g_s, float* g_nproj, int ldn, float* g_x, float* g_v,
                         float* g_X_out, float* g_rl, float* g_cut, float* ga_parts, long E,
                         int N, int F, int H, int lmax, int sep_dir, int sep_tensor, int act, void* stream);
+/* ... of a layer whose forward ran gn_attn_softmax_dropout: a = the dropped weights (what the message stage used), a_soft the
+ * undropped ones.  With dot = sum_e' a[e'] g_a[e'] over the target's edges, g_s[e] = a[e] g_a[e] - (a_soft[e] / nrm_e) dot;
+ * every other term is gn_message_backward's with `a`.  No random numbers are drawn. */
+int gn_message_backward_dropout(const float* x, const float* v, int ldxv, const float* eproj, int lde, const float* a,
+                                const float* a_soft,
+                                const float* qk, int ldqk, const float* X_in, const float* rl, const float* cut,
+                                const int* outdeg, const float* g_h1, const float* g_X1,
+                                const int* rowptr, const int* src, const int* tgt_by_src, const int* colptr, const int* perm,
+                                float* g_eproj, float* g_s, float* g_nproj, int ldn, float* g_x, float* g_v,
+                                float* g_X_out, float* g_rl, float* g_cut, float* ga_parts, long E,
+                                int N, int F, int H, int lmax, int sep_dir, int sep_tensor, int act, void* stream);
 /* Number of degree groups G the message backward uses for these flags (1 = monolithic kernels, lmax >= 5, and every
  * activation other than GN_ACT_SILU -- those run the degree-sliced kernels; lmax 3..4 with sep_dir and sep_tensor
  * and SiLU: {scalar,1,2}, {3}, {4}).  g_cut must then hold G consecutive [E] slices and ga_parts

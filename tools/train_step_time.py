@@ -10,6 +10,12 @@ and a reduction kernel per 8 problems) and their FLOP rate, and -- on its own, b
 g_eproj^T t ([(1+M)F x F] over the E edge rows), against the fp32 MFMA peak.  ``--json PATH`` also writes the record.
 
     python tools/train_step_time.py --steps 20 --warmup 5 --json profiles/train_step_time.json
+
+``--attn-dropout P[,P...]`` times every shape once per attention-dropout probability (the modules are in train() mode, so
+P > 0 runs the dropout kernels: one more [E,H] write per layer forward, one more [E,H] read per layer backward, one key
+launch per call), same weights and inputs:
+
+    python tools/train_step_time.py --shapes c2 --attn-dropout 0,0.1 --json profiles/train_step_dropout.json
 """
 from __future__ import annotations
 
@@ -70,7 +76,7 @@ def _dwe_alone(E: int, F: int, M: int, reps: int = 20):
                 frac_of_fp32_mfma_peak=round(tf / FP32_MFMA_PEAK_TFLOPS, 3))
 
 
-def run(shape: str, steps: int, warmup: int):
+def run(shape: str, steps: int, warmup: int, attn_dropout: float = 0.0):
     import gotennet_amd
     from gotennet_amd import _lib
     from gotennet_amd.outputs import Atomwise
@@ -78,7 +84,8 @@ def run(shape: str, steps: int, warmup: int):
     sp = SHAPES[shape]
     torch.manual_seed(0)
     net = gotennet_amd.GotenNetWrapper(cutoff_fn=gotennet_amd.CosineCutoff(5.0), num_heads=8, scale_edge=False,
-                                       sep_dir=True, sep_tensor=True, max_z=10, **sp["model"]).cuda().train()
+                                       sep_dir=True, sep_tensor=True, max_z=10, attn_dropout=attn_dropout,
+                                       **sp["model"]).cuda().train()
     head = Atomwise(n_in=256, n_hidden=128, activation="silu").cuda().train()
     net.parameter_grads = head.parameter_grads = True
     pos, batch, z = make_batch(sp["workload"], sp["n_mol"])
@@ -113,7 +120,7 @@ def run(shape: str, steps: int, warmup: int):
     wg_ms = sum(a.elapsed_time(b) for _, a, b in timer.events)
     from gotennet_amd.graph import distance
     E = int(distance(inp.pos, inp.batch, net.cutoff, net.max_num_neighbors)[0].shape[1])
-    return dict(shape=shape, n_mol=sp["n_mol"], atoms=int(z.shape[0]), edges=E, ms_per_step=round(ms, 3),
+    return dict(shape=shape, attn_dropout=attn_dropout, n_mol=sp["n_mol"], atoms=int(z.shape[0]), edges=E, ms_per_step=round(ms, 3),
                 molecules_per_s=round(sp["n_mol"] / ms * 1e3, 1), wgrad_ms=round(wg_ms, 3),
                 wgrad_calls=len(timer.events), wgrad_kernels=timer.kernels, wgrad_gflop=round(timer.flops / 1e9, 2),
                 wgrad_tflops=round(timer.flops / wg_ms / 1e9, 2) if wg_ms > 0 else None,
@@ -126,8 +133,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--shapes", default="qm9,c2")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--attn-dropout", default="0", help="comma-separated attention-dropout probabilities, one run each")
     a = ap.parse_args()
-    out = [run(s, a.steps, a.warmup) for s in a.shapes.split(",")]
+    out = [run(s, a.steps, a.warmup, float(p)) for s in a.shapes.split(",") for p in a.attn_dropout.split(",")]
     for r in out:
         print(json.dumps(r), flush=True)
     if a.json:
