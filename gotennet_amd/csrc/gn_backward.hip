@@ -20,93 +20,109 @@
 
 namespace gn {
 
-
-
 // The register-tiled kernels of this file are compiled for SiLU (the reference's default activation, and what every
 // benchmarked configuration uses): with the activation kind as a run-time switch the other eleven kinds' code cost
 // 4..22 VGPRs and a spill in msg_bwd_source (+4.5 % on the whole step).  Models with another activation take the
 // degree-sliced kernels of gn_highl.hip, which carry the kind as a run-time value.
-// =========================================================================== HTR backward
-// w = sum_l [ A.B - (2 - r.r)(A.r)(B.r) ],  A = EQ_i block, B = EK_j block, r = rl block
-template <int LMAX, int FC = 0>
-__global__ __launch_bounds__(256) GN_WPE(GN_W_HTR_TGT) void htr_bwd_target_kernel(
-    const float* __restrict__ gtp, const float* __restrict__ pre_t, const float* __restrict__ w,
-    const float* __restrict__ EQ, const float* __restrict__ EK, const float* __restrict__ rl,
-    const int* __restrict__ rowptr, const int* __restrict__ src, int N, int F_rt,
-    float* __restrict__ gEQ, float* __restrict__ g_rl, float* __restrict__ g_pre_t, int /* act: GN_ACT_SILU on this path, see gn_htr_backward */) {
-    constexpr int act = GN_ACT_SILU;
-    constexpr int D = (LMAX + 1) * (LMAX + 1) - 1;
-    constexpr int KP = D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32));
-    constexpr int CH = D < 9 ? D : 9;
-    __shared__ __attribute__((aligned(16))) float red[CH * 1024];
-    const int F = FC ? FC : F_rt;
-    const int i = xcd_item(blockIdx.x, N);
-    if (i < 0) return;
-    GN_SLOT_GEOMETRY(FC);
-    const int e0 = rowptr[i], e1 = rowptr[i + 1];
-    float4 eq[D], acc[D];
+
+// =========================================================================== pieces shared by the gather kernels
+// Sums of K per-edge values over the lanes of a slot, stored to arr[base .. base + K) by one lane per value.  Padded to a
+// power of two KP, all K sums share ONE value-halving butterfly when lps >= KP; otherwise a group_sum per value.
+// (array and offset apart, as the bodies index their __restrict__ parameter: with the sum formed by the caller the kernels
+//  of padded K came out with other register counts)
+template <int K>
+__device__ __forceinline__ void slot_sums(const float (&v)[K], int lps, int lp, float* __restrict__ arr, size_t base) {
+    constexpr int KP = K <= 4 ? 4 : (K <= 8 ? 8 : (K <= 16 ? 16 : 32));
+    if (lps >= KP) {
+        float vals[KP];
 #pragma unroll
-    for (int m = 0; m < D; ++m) { eq[m] = ld4(EQ + ((size_t)i * D + m) * F + c0); acc[m] = zero4(); }
-    for (int e = e0 + slot; e < e1; e += ns) {
-        const float4 gte = ld4(gtp + (size_t)e * F + c0), pte = ld4(pre_t + (size_t)e * F + c0);
-        float4 a_pt, d_pt;
-        act_pair4(pte, act, a_pt, d_pt);
-        const float4 gw = gte * a_pt;
-        // t' = t + SiLU(pre_t) * w:  d/d pre_t, ready for the plain W_t^T product that follows
-        // (w is read here and nowhere else after K7 wrote it: non-temporal; step 7.555 / 7.534 -> 7.532 / 7.513 ms.  A non-temporal
-        //  g_pre_t store measured nothing: the W_t^T product reads it next)
-        st4(g_pre_t + (size_t)e * F + c0, gte * ld4_nt(w + (size_t)e * F + c0) * d_pt);
-        const float* kj = EK + (size_t)src[e] * D * F + c0;
-        const float* re = rl + (size_t)e * D;
-        float part[KP];
+        for (int k = 0; k < KP; ++k) vals[k] = k < K ? v[k] : 0.f;
+        multi_group_sum<KP>(vals, lps, lp);
+        const int stride = lps / KP;
+        if ((lp & (stride - 1)) == 0 && lp / stride < K) arr[base + lp / stride] = vals[0];
+    } else {
 #pragma unroll
-        for (int m = D; m < KP; ++m) part[m] = 0.f;
-        int m0 = 0;
-#pragma unroll
-        for (int l = 1; l <= LMAX; ++l) {
-            float4 ek[2 * LMAX + 1];
-            float r[2 * LMAX + 1];
-            float4 pa = zero4(), pb = zero4();
-            float rr = 0.f;
-#pragma unroll
-            for (int mm = 0; mm < 2 * l + 1; ++mm) {
-                ek[mm] = ld4(kj + (size_t)(m0 + mm) * F);
-                r[mm] = re[m0 + mm];
-                pa = fma4(r[mm], eq[m0 + mm], pa);
-                pb = fma4(r[mm], ek[mm], pb);
-                rr = fmaf(r[mm], r[mm], rr);
-            }
-            // gw factored out of the per-row terms: u = -c gw pb, v = -c gw pa, s = 2 gw pa pb
-            const float c = 2.0f - rr;
-            const float4 u = gw * pb * (-c), v = gw * pa * (-c), s2 = gw * (pa * pb) * 2.0f;
-#pragma unroll
-            for (int mm = 0; mm < 2 * l + 1; ++mm) {
-                acc[m0 + mm] = fma4(r[mm], u, fma4(gw, ek[mm], acc[m0 + mm]));
-                part[m0 + mm] = hsum4(fma4(r[mm], s2, fma4(v, ek[mm], u * eq[m0 + mm])));
-            }
-            m0 += 2 * l + 1;
-        }
-        if (lps >= KP) {                             // one value-halving butterfly for all D sums
-            multi_group_sum<KP>(part, lps, lp);
-            const int stride = lps / KP;
-            if ((lp & (stride - 1)) == 0 && lp / stride < D) g_rl[(size_t)e * D + lp / stride] = part[0];
-        } else {
-#pragma unroll
-            for (int m = 0; m < D; ++m) {
-                const float s = group_sum(part[m], lps);
-                if (lp == 0) g_rl[(size_t)e * D + m] = s;
-            }
+        for (int k = 0; k < K; ++k) {
+            const float s = group_sum(v[k], lps);
+            if (lp == 0) arr[base + k] = s;
         }
     }
-    reduce_rows<D>(acc, red, slot, c0, F, ns, [&](int row, float4 s) { st4(gEQ + ((size_t)i * D + row) * F + c0, s); });
 }
 
+// Head sums of one edge: head h owns the flattened float4 positions [h PH, (h+1) PH) of the (block, lane) grid of the MS
+// value blocks, PH = MS lps / H.  The caller has staged the per-lane partials of the blocks it computes in the slot's LDS
+// row, hrow[b * lps + lp] (MS * lps floats; a slot never spans waves: wave-ordered LDS accesses, no barrier); lps / H reader
+// lanes per head add MS consecutive entries each, then a short butterfly, and out[h] gets the sum.  (Per-head selects cost
+// 8 M compare/select pairs per edge and 77 spilled mask SGPRs.  The staging loop stays with the caller: with the partials
+// passed in as a register array the kernels of the F != 256 forms came out 2 .. 6 VGPRs larger.)
+template <int MS>
+__device__ __forceinline__ void slot_head_sums(const float* hrow, int lps, int lp, int H, float* __restrict__ out) {
+    const int rpl = lps / H, hh = lp / rpl, part = lp - hh * rpl;
+    const float* hp = hrow + hh * (MS * rpl) + part * MS;
+    float hv = hp[0];
+#pragma unroll
+    for (int k = 1; k < MS; ++k) hv += hp[k];
+    hv = group_sum(hv, rpl);
+    if (part == 0) out[hh] = hv;
+}
+
+// The head gradients g_a -> g_s of one target (rows [e0, e1) of the CSR order).  GS_LDS: they stay in LDS between the phases
+// of the attention backward (deg * H <= GS_CAP floats) and reach the global g_s rows (read by the by-source pass) in ONE
+// coalesced copy; otherwise they go through those rows (three dependent global round trips per workgroup).  Same
+// arithmetic, same order in both forms.
+constexpr int GS_CAP = 2048;
+template <bool GS_LDS>
+struct HeadGrads {
+    float* gsl; float* g_s; int e0, H;
+    __device__ __forceinline__ float& operator()(int e, int h) const {
+        if constexpr (GS_LDS) return gsl[(e - e0) * H + h];
+        else return g_s[(size_t)e * H + h];
+    }
+    __device__ __forceinline__ void copy_out(int e1) const {      // (after a barrier; no-op when they are in g_s already)
+        if constexpr (GS_LDS) {
+            const int n = (e1 - e0) * H;
+            for (int idx = threadIdx.x; idx < n; idx += 256) g_s[(size_t)e0 * H + idx] = gsl[idx];
+        }
+    }
+};
+// softmax backward of one target, one head (a wave): GS holds the head's g_a on entry, dot = sum_e a g_a over the target's
+// edges; on return GS holds g_s = a g_a - (a_soft / nrm) dot  (a_soft = a without dropout, or NULL).  The loop that forms
+// dot stays with the caller: it is where the two users differ (g_a already in GS / summed from the groups' slices), and as
+// a callback argument it moved registers and occupancy of the by-target kernels.
+template <typename Grads>
+__device__ __forceinline__ void softmax_bwd_head(int e0, int e1, int H, int h, float dot, const float* __restrict__ a,
+                                                 const float* __restrict__ a_soft, const int* __restrict__ outdeg,
+                                                 const int* __restrict__ src, float inv_sqrt_f, Grads GS) {
+    for (int e = e0 + (threadIdx.x & 63); e < e1; e += 64) {
+        const float nrm = outdeg ? sqrtf((float)outdeg[src[e]]) * inv_sqrt_f : inv_sqrt_f;
+        const float av = a[(size_t)e * H + h];
+        const float sv = a_soft ? a_soft[(size_t)e * H + h] : av;
+        GS(e, h) = av * GS(e, h) - (sv / nrm) * dot;
+    }
+}
+// scores backward of one edge, target side: g_q += g_s k_j SiLU(pre_ta), and the g_eproj attention column
+// d/d(pre-activation of t_attn) = g_s (q_i k_j) SiLU'(pre_ta) ...
+__device__ __forceinline__ void score_bwd_edge(float gs, float4 qi, float4 kj, float4 pta, float4& gq, float* __restrict__ g_pta) {
+    float4 a_ta, d_ta;
+    act_pair4(pta, GN_ACT_SILU, a_ta, d_ta);
+    gq = fma4(gs, kj * a_ta, gq);
+    st4_nt(g_pta, ((qi * kj) * gs) * d_ta);
+}
+// ... and source side: g_k += g_s q_i SiLU(pre_ta)
+__device__ __forceinline__ float4 score_bwd_edge_k(float gs, float4 qi, float4 pta, float4 gk) {
+    return fma4(gs, qi * act4(pta, GN_ACT_SILU), gk);
+}
+
+// =========================================================================== HTR backward
+// w = sum_l [ A.B - (2 - r.r)(A.r)(B.r) ],  A = EQ_i block, B = EK_j block, r = rl block
+// (the by-target pass is htr_bwd_target_group_kernel, below with the degree groups)
+// by source at lmax <= 2.  Not folded into htr_bwd_source_group_kernel: fma4(r, v, fma4(gw, eq, acc)) here, other bits there
 template <int LMAX, int FC = 0>
 __global__ __launch_bounds__(256) GN_WPE(GN_W_HTR_SRC) void htr_bwd_source_kernel(
     const float* __restrict__ gtp, const float* __restrict__ pre_t,
     const float* __restrict__ EQ, const float* __restrict__ EK, const float* __restrict__ rl,
     const int* __restrict__ colptr, const int* __restrict__ perm, const int* __restrict__ dst, int N, int F_rt,
-    float* __restrict__ gEK, int /* act: GN_ACT_SILU on this path, see gn_htr_backward */) {
+    float* __restrict__ gEK) {
     constexpr int act = GN_ACT_SILU;
     constexpr int D = (LMAX + 1) * (LMAX + 1) - 1;
     constexpr int CH = D < 9 ? D : 9;
@@ -166,17 +182,14 @@ struct MsgShape {
 // by-target pass: g_tf, g_cut, g_rl, attention backward (g_a -> g_s), g_ta, g_q
 // (body in a forceinline function with __restrict__ parameters: with the pointers read from the argument struct the
 //  compiler had to assume that the g_eproj stores alias every later load and issued the row loads one at a time)
-// GS_LDS: the head gradients g_a -> g_s of this target stay in LDS between the three phases (deg * H <= GS_CAP floats)
-// and reach the global g_s rows (read by the by-source pass) in ONE coalesced copy; otherwise they go through those rows
-// like in round 2 (three dependent global round trips per workgroup).  Same arithmetic, same order in both forms.
-constexpr int GS_CAP = 2048;
+// GS_LDS: where the head gradients of this target live between the three phases (HeadGrads above).
 // FIRST: X_in is identically zero (first interaction): every tensor-gate term vanishes -- those blocks of eproj / x / v
 // are not read, their g_eproj columns not written (the W_e^T product that follows takes the K-prefix).
+// The pointer parameters are filled positionally by GN_MSGB_TARGET_PTRS below: change the two together.
 template <int LMAX, bool SEP_DIR, bool SEP_TENSOR, bool GS_LDS, bool FIRST, int FC>
 __device__ __forceinline__ void msg_bwd_target_body(const MsgBwdArgs& p, float* gsl, float* red, float* hsum, const float* __restrict__ x_, const float* __restrict__ v_, const float* __restrict__ eproj_, const float* __restrict__ a_, const float* __restrict__ qk_, const float* __restrict__ X_in_, const float* __restrict__ rl_, const float* __restrict__ cut_, const int* __restrict__ outdeg_, const float* __restrict__ g_h1_, const float* __restrict__ g_X1_, const int* __restrict__ rowptr_, const int* __restrict__ src_, float* __restrict__ g_eproj_, float* __restrict__ g_s_, float* __restrict__ g_nproj_, float* __restrict__ g_rl_, float* __restrict__ g_cut_) {
     using S = MsgShape<LMAX, SEP_DIR, SEP_TENSOR>;
     constexpr int D = S::D, M = S::M;
-    constexpr int KP = D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32));      // D rl sums, padded to a power of two
     const int N = p.N, F = FC ? FC : p.F, H = p.H;
     const int i = xcd_item(blockIdx.x, N);
     if (i < 0) return;
@@ -186,10 +199,7 @@ __device__ __forceinline__ void msg_bwd_target_body(const MsgBwdArgs& p, float* 
     int hb[M];
 #pragma unroll
     for (int b = 0; b < M; ++b) hb[b] = (b * F + c0) / per_head;
-    auto GS = [&](int e, int h) -> float& {
-        if constexpr (GS_LDS) return gsl[(e - e0) * H + h];
-        else return g_s_[(size_t)e * H + h];
-    };
+    const HeadGrads<GS_LDS> GS{gsl, g_s_, e0, H};
 
     const float4 gdh = ld4(g_h1_ + (size_t)i * F + c0);
     float4 gdX[D];
@@ -240,36 +250,11 @@ __device__ __forceinline__ void msg_bwd_target_body(const MsgBwdArgs& p, float* 
         }
         cutp = group_sum(cutp, lps);
         if (lp == 0) g_cut_[e] = cutp;
-        // head sums: head h owns the flattened float4 positions [h PH, (h+1) PH) of the (block, lane) grid,
-        // PH = M lps / H.  Stage the M per-lane partials in LDS (a slot never spans waves: wave-ordered LDS
-        // accesses, no barrier), lps / H reader lanes per head add M consecutive entries each, then a short
-        // butterfly.  (Per-head selects cost 8 M compare/select pairs per edge and 77 spilled mask SGPRs.)
-        {
-            float* hrow = hsum + slot * (M * lps);
+        float* hrow = hsum + slot * (M * lps);
 #pragma unroll
-            for (int b = 0; b < M; ++b) hrow[b * lps + lp] = pa_h[b];
-            const int rpl = lps / H, hh = lp / rpl, part = lp - hh * rpl;
-            const float* hp = hrow + hh * (M * rpl) + part * M;
-            float hv = hp[0];
-#pragma unroll
-            for (int k = 1; k < M; ++k) hv += hp[k];
-            hv = group_sum(hv, rpl);
-            if (part == 0) GS(e, hh) = hv;
-        }
-        if (lps >= KP) {                             // D rl sums in one butterfly
-            float vals[KP];
-#pragma unroll
-            for (int m = 0; m < KP; ++m) vals[m] = m < D ? rlp[m] : 0.f;
-            multi_group_sum<KP>(vals, lps, lp);
-            const int stride = lps / KP;
-            if ((lp & (stride - 1)) == 0 && lp / stride < D) g_rl_[(size_t)e * D + lp / stride] = vals[0];
-        } else {
-#pragma unroll
-            for (int m = 0; m < D; ++m) {
-                const float s = group_sum(rlp[m], lps);
-                if (lp == 0) g_rl_[(size_t)e * D + m] = s;
-            }
-        }
+        for (int b = 0; b < M; ++b) hrow[b * lps + lp] = pa_h[b];
+        slot_head_sums<M>(hrow, lps, lp, H, &GS(e, 0));
+        slot_sums(rlp, lps, lp, g_rl_, (size_t)e * D);
     }
     // phase 3's rows of this slot's first PF3 edges are requested HERE, ahead of the two barriers of phase 2: they do not
     // depend on it, and fetched inside phase 3 each trip exposes one HBM round trip (t_attn row) with two loads in flight
@@ -284,20 +269,13 @@ __device__ __forceinline__ void msg_bwd_target_body(const MsgBwdArgs& p, float* 
         }
     }
     __syncthreads();
-    // ---- phase 2: softmax backward per head:  g_s = a g_a - (a_soft / nrm) sum_e' a g_a  (a_soft = a without dropout)
+    // ---- phase 2: softmax backward per head (phase 1 left g_a in GS)
     {
-        const float* __restrict__ as_ = p.a_soft;
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
         for (int h = wave; h < H; h += 4) {
             float dot = 0.f;
             for (int e = e0 + lane; e < e1; e += 64) dot += a_[(size_t)e * H + h] * GS(e, h);
-            dot = wave_sum(dot);
-            for (int e = e0 + lane; e < e1; e += 64) {
-                const float nrm = outdeg_ ? sqrtf((float)outdeg_[src_[e]]) * p.inv_sqrt_f : p.inv_sqrt_f;
-                const float av = a_[(size_t)e * H + h];
-                const float sv = as_ ? as_[(size_t)e * H + h] : av;
-                GS(e, h) = av * GS(e, h) - (sv / nrm) * dot;
-            }
+            softmax_bwd_head(e0, e1, H, h, wave_sum(dot), a_, p.a_soft, outdeg_, src_, p.inv_sqrt_f, GS);
         }
     }
     __syncthreads();
@@ -305,17 +283,8 @@ __device__ __forceinline__ void msg_bwd_target_body(const MsgBwdArgs& p, float* 
     const int hq = c0 / (F / H);
     const float4 qi = ld4(qk_ + (size_t)i * p.ldqk + c0);
     float4 gq = zero4();
-    if constexpr (GS_LDS) {
-        const int n = (e1 - e0) * H;
-        for (int idx = threadIdx.x; idx < n; idx += 256) g_s_[(size_t)e0 * H + idx] = gsl[idx];
-    }
-    auto score_bwd = [&](int e, float4 kj, float4 pta) {
-        const float gs = GS(e, hq);
-        float4 a_ta, d_ta;
-        act_pair4(pta, GN_ACT_SILU, a_ta, d_ta);
-        gq = fma4(gs, kj * a_ta, gq);
-        st4_nt(g_eproj_ + (size_t)e * p.lde + c0, ((qi * kj) * gs) * d_ta);   // d/d(pre-activation of t_attn)
-    };
+    GS.copy_out(e1);
+    auto score_bwd = [&](int e, float4 kj, float4 pta) { score_bwd_edge(GS(e, hq), qi, kj, pta, gq, g_eproj_ + (size_t)e * p.lde + c0); };
 #pragma unroll
     for (int u = 0; u < PF3; ++u) {
         const int e = e0 + slot + u * ns;
@@ -328,6 +297,9 @@ __device__ __forceinline__ void msg_bwd_target_body(const MsgBwdArgs& p, float* 
     if (slot == 0) st4(g_nproj_ + (size_t)i * p.ldn + c0, red4(red, c0, F, ns));
 }
 
+#define GN_MSGB_TARGET_PTRS(p)                                                                                        \
+    p.x, p.v, p.eproj, p.a, p.qk, p.X_in, p.rl, p.cut, p.outdeg, p.g_h1, p.g_X1, p.rowptr, p.src, p.g_eproj, p.g_s, p.g_nproj, \
+        p.g_rl, p.g_cut
 template <int LMAX, bool SEP_DIR, bool SEP_TENSOR, bool FIRST = false, int FC = 0>
 __global__ __launch_bounds__(256) GN_WPE(GN_W_MSG_TGT) void msg_bwd_target_kernel(const MsgBwdArgs p) {
     __shared__ __attribute__((aligned(16))) float red[1024];
@@ -336,10 +308,11 @@ __global__ __launch_bounds__(256) GN_WPE(GN_W_MSG_TGT) void msg_bwd_target_kerne
     const int i = xcd_item(blockIdx.x, p.N);
     if (i < 0) return;
     if ((p.rowptr[i + 1] - p.rowptr[i]) * p.H <= GS_CAP)      // workgroup-uniform, decided once
-        msg_bwd_target_body<LMAX, SEP_DIR, SEP_TENSOR, true, FIRST, FC>(p, gsl, red, hsum, p.x, p.v, p.eproj, p.a, p.qk, p.X_in, p.rl, p.cut, p.outdeg, p.g_h1, p.g_X1, p.rowptr, p.src, p.g_eproj, p.g_s, p.g_nproj, p.g_rl, p.g_cut);
+        msg_bwd_target_body<LMAX, SEP_DIR, SEP_TENSOR, true, FIRST, FC>(p, gsl, red, hsum, GN_MSGB_TARGET_PTRS(p));
     else
-        msg_bwd_target_body<LMAX, SEP_DIR, SEP_TENSOR, false, FIRST, FC>(p, gsl, red, hsum, p.x, p.v, p.eproj, p.a, p.qk, p.X_in, p.rl, p.cut, p.outdeg, p.g_h1, p.g_X1, p.rowptr, p.src, p.g_eproj, p.g_s, p.g_nproj, p.g_rl, p.g_cut);
+        msg_bwd_target_body<LMAX, SEP_DIR, SEP_TENSOR, false, FIRST, FC>(p, gsl, red, hsum, GN_MSGB_TARGET_PTRS(p));
 }
+#undef GN_MSGB_TARGET_PTRS
 
 // by-source pass: g_x, g_v, g_k, and g_X (tensor-gate path) of the gathered source rows
 // FIRST (X_in == 0): no g_X rows (nothing consumes the gradient of a constant), tensor-gate blocks of g_x / g_v are zero
@@ -408,10 +381,8 @@ __global__ __launch_bounds__(256) GN_WPE(GN_W_MSG_SRC) void msg_bwd_source_kerne
             acc[b] = fma4(go, tfb * ce, acc[b]);
             acc[M + b] = fma4(ab, go, acc[M + b]);
         }
-        const float gs = p.g_s[(size_t)e * H + hq];
-        const float4 qi = ld4(p.qk + (size_t)i * p.ldqk + c0);
-        const float4 ta = act4(ld4_nt(p.eproj + (size_t)e * p.lde + c0), GN_ACT_SILU);
-        acc[2 * M + XD] = fma4(gs, qi * ta, acc[2 * M + XD]);
+        acc[2 * M + XD] = score_bwd_edge_k(p.g_s[(size_t)e * H + hq], ld4(p.qk + (size_t)i * p.ldqk + c0),
+                                           ld4_nt(p.eproj + (size_t)e * p.lde + c0), acc[2 * M + XD]);
     }
     reduce_rows<ROWS>(acc, red, slot, c0, F, ns, [&](int row, float4 s) {
         if (row < M) st4(p.g_x + (size_t)j * p.ldxv + row * F + c0, s);
@@ -441,6 +412,7 @@ __global__ __launch_bounds__(256) GN_WPE(GN_W_MSG_SRC) void msg_bwd_source_kerne
 // FIRST: X_in is identically zero (first interaction): only the scalar and the direction-gate blocks exist -- the tensor-gate
 // blocks of eproj / x / v are not read, their g_eproj columns not written, those blocks of g_x / g_v are written as zeros,
 // no X rows, no g_X (as in the FIRST forms of the by-target / by-source pair, which this replaces when ga is given).
+// The parameters up to g_rl are filled positionally by GN_MSGB_SOURCE_PTRS below: change the two together.
 template <int LMAX, bool SEP_DIR, bool SEP_TENSOR, int FC, bool FIRST>
 __device__ __forceinline__ void msg_bwd_merged_body(
     const float* __restrict__ x, const float* __restrict__ v, int ldxv, const float* __restrict__ X_in,
@@ -451,7 +423,6 @@ __device__ __forceinline__ void msg_bwd_merged_body(
     float* __restrict__ g_rl, float* __restrict__ g_cut, float* __restrict__ ga, int N, int F_rt, int H) {
     using S = MsgShape<LMAX, SEP_DIR, SEP_TENSOR>;
     constexpr int D = S::D, M = S::M;
-    constexpr int KP = D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32));
     constexpr int MB = FIRST ? 1 + S::ND : M;         // value blocks this launch handles
     constexpr int XR = FIRST ? 0 : D;                 // X rows / g_X rows
     constexpr int ROWS = 2 * MB + XR;                 // [0,MB) g_x, [MB,2MB) g_v, [2MB, 2MB+D) g_X
@@ -543,32 +514,12 @@ __device__ __forceinline__ void msg_bwd_merged_body(
         }
         cutp = group_sum(cutp, lps);
         if (lp == 0) g_cut[e] = cutp;
-        {   // head sums of g_a (same staging as msg_bwd_target_body: a slot never spans waves, wave-ordered LDS accesses)
-            float* hrow = hsum + slot * (M * lps);  // (heads are cut from ALL M blocks of the value vector: FIRST leaves the rest zero)
+        // head sums of g_a: heads are cut from ALL M blocks of the value vector (FIRST left the rest of the row zero)
+        float* hrow = hsum + slot * (M * lps);
 #pragma unroll
-            for (int b = 0; b < MB; ++b) hrow[b * lps + lp] = pa_h[b];
-            const int rpl = lps / H, hh = lp / rpl, part = lp - hh * rpl;
-            const float* hp = hrow + hh * (M * rpl) + part * M;
-            float hv = hp[0];
-#pragma unroll
-            for (int k = 1; k < M; ++k) hv += hp[k];
-            hv = group_sum(hv, rpl);
-            if (part == 0) ga[(size_t)e * H + hh] = hv;
-        }
-        if (lps >= KP) {                             // D rl sums in one butterfly
-            float vals[KP];
-#pragma unroll
-            for (int m = 0; m < KP; ++m) vals[m] = m < D ? rlp[m] : 0.f;
-            multi_group_sum<KP>(vals, lps, lp);
-            const int stride = lps / KP;
-            if ((lp & (stride - 1)) == 0 && lp / stride < D) g_rl[(size_t)e * D + lp / stride] = vals[0];
-        } else {
-#pragma unroll
-            for (int m = 0; m < D; ++m) {
-                const float sv = group_sum(rlp[m], lps);
-                if (lp == 0) g_rl[(size_t)e * D + m] = sv;
-            }
-        }
+        for (int b = 0; b < MB; ++b) hrow[b * lps + lp] = pa_h[b];
+        slot_head_sums<M>(hrow, lps, lp, H, ga + (size_t)e * H);
+        slot_sums(rlp, lps, lp, g_rl, (size_t)e * D);
     }
     reduce_rows<ROWS>(acc, red, slot, c0, F, ns, [&](int row, float4 sv) {
         if (row < MB) st4(g_x + (size_t)j * ldxv + row * F + c0, sv);
@@ -584,20 +535,18 @@ __device__ __forceinline__ void msg_bwd_merged_body(
             st4(g_v + (size_t)j * ldxv + b * F + c0, zero4());
         }
 }
+// the leading (__restrict__) parameters of the merged bodies, this one and the degree-group one, from the argument struct
+#define GN_MSGB_SOURCE_PTRS(p)                                                                                        \
+    p.x, p.v, p.ldxv, p.X_in, p.eproj, p.lde, p.a, p.rl, p.cut, p.g_h1, p.g_X1, p.dst, p.colptr, p.perm, p.g_eproj, p.g_x, p.g_v, \
+        p.g_X_out, p.g_rl
 // (occupancy hints per form, gn_tune.h: the general launch runs best without one, the first-interaction form at 2 waves per SIMD)
 template <int LMAX, bool SEP_DIR, bool SEP_TENSOR, int FC = 0>
 __global__ __launch_bounds__(256) GN_WPE(GN_W_MSG_MRG) void msg_bwd_merged_kernel(const MsgBwdArgs p, float* __restrict__ ga) {
-
-    msg_bwd_merged_body<LMAX, SEP_DIR, SEP_TENSOR, FC, false>(p.x, p.v, p.ldxv, p.X_in, p.eproj, p.lde, p.a, p.rl, p.cut, p.g_h1, p.g_X1,
-                                                        p.dst, p.colptr, p.perm, p.g_eproj, p.g_x, p.g_v, p.g_X_out, p.g_rl,
-                                                        p.g_cut, ga, p.N, p.F, p.H);
+    msg_bwd_merged_body<LMAX, SEP_DIR, SEP_TENSOR, FC, false>(GN_MSGB_SOURCE_PTRS(p), p.g_cut, ga, p.N, p.F, p.H);
 }
 template <int LMAX, bool SEP_DIR, bool SEP_TENSOR, int FC = 0>
 __global__ __launch_bounds__(256) GN_WPE(GN_W_MSG_MRG_F) void msg_bwd_merged_first_kernel(const MsgBwdArgs p, float* __restrict__ ga) {
-
-    msg_bwd_merged_body<LMAX, SEP_DIR, SEP_TENSOR, FC, true>(p.x, p.v, p.ldxv, p.X_in, p.eproj, p.lde, p.a, p.rl, p.cut, p.g_h1, p.g_X1,
-                                                        p.dst, p.colptr, p.perm, p.g_eproj, p.g_x, p.g_v, p.g_X_out, p.g_rl,
-                                                        p.g_cut, ga, p.N, p.F, p.H);
+    msg_bwd_merged_body<LMAX, SEP_DIR, SEP_TENSOR, FC, true>(GN_MSGB_SOURCE_PTRS(p), p.g_cut, ga, p.N, p.F, p.H);
 }
 
 // g_k of the gathered source rows, after the softmax backward:  g_k_j = sum_e g_s[e, head] q_i SiLU(t_attn pre-activation)
@@ -612,10 +561,8 @@ __global__ __launch_bounds__(256) void msg_bwd_gk_kernel(const MsgBwdArgs p) {
     float4 gk[1] = {zero4()};
     for (int pp = p.colptr[j] + slot; pp < p.colptr[j + 1]; pp += ns) {
         const int e = p.perm[pp], i = p.dst[pp];
-        const float gs = p.g_s[(size_t)e * H + hq];
-        const float4 qi = ld4(p.qk + (size_t)i * p.ldqk + c0);
-        const float4 ta = act4(ld4_nt(p.eproj + (size_t)e * p.lde + c0), GN_ACT_SILU);
-        gk[0] = fma4(gs, qi * ta, gk[0]);
+        gk[0] = score_bwd_edge_k(p.g_s[(size_t)e * H + hq], ld4(p.qk + (size_t)i * p.ldqk + c0),
+                                 ld4_nt(p.eproj + (size_t)e * p.lde + c0), gk[0]);
     }
     reduce_rows<1>(gk, red, slot, c0, F, ns, [&](int, float4 sv) { st4(p.g_nproj + (size_t)j * p.ldn + F + c0, sv); });
 }
@@ -633,10 +580,7 @@ __device__ __forceinline__ void attn_bwd_body(const MsgBwdArgs& p, const float* 
     const int F = FC ? FC : p.F, H = p.H;
     GN_SLOT_GEOMETRY(FC);
     const int e0 = p.rowptr[i], e1 = p.rowptr[i + 1];
-    auto GS = [&](int e, int h) -> float& {
-        if constexpr (GS_LDS) return gsl[(e - e0) * H + h];
-        else return p.g_s[(size_t)e * H + h];
-    };
+    const HeadGrads<GS_LDS> GS{gsl, p.g_s, e0, H};
     {
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
         for (int h = wave; h < H; h += 4) {
@@ -647,31 +591,17 @@ __device__ __forceinline__ void attn_bwd_body(const MsgBwdArgs& p, const float* 
                 GS(e, h) = ga;
                 dot += p.a[(size_t)e * H + h] * ga;
             }
-            dot = wave_sum(dot);
-            for (int e = e0 + lane; e < e1; e += 64) {
-                const float nrm = p.outdeg ? sqrtf((float)p.outdeg[p.src[e]]) * p.inv_sqrt_f : p.inv_sqrt_f;
-                const float av = p.a[(size_t)e * H + h];
-                const float sv = p.a_soft ? p.a_soft[(size_t)e * H + h] : av;
-                GS(e, h) = av * GS(e, h) - (sv / nrm) * dot;
-            }
+            softmax_bwd_head(e0, e1, H, h, wave_sum(dot), p.a, p.a_soft, p.outdeg, p.src, p.inv_sqrt_f, GS);
         }
     }
     __syncthreads();
-    if constexpr (GS_LDS) {
-        const int n = (e1 - e0) * H;
-        for (int idx = threadIdx.x; idx < n; idx += 256) p.g_s[(size_t)e0 * H + idx] = gsl[idx];
-    }
+    GS.copy_out(e1);
     const int hq = c0 / (F / H);
     const float4 qi = ld4(p.qk + (size_t)i * p.ldqk + c0);
     float4 gq = zero4();
     for (int e = e0 + slot; e < e1; e += ns) {
-        const float gs = GS(e, hq);
         const float4 kj = ld4(p.qk + (size_t)p.src[e] * p.ldqk + F + c0);
-        const float4 pta = ld4_nt(p.eproj + (size_t)e * p.lde + c0);
-        float4 a_ta, d_ta;
-        act_pair4(pta, GN_ACT_SILU, a_ta, d_ta);
-        gq = fma4(gs, kj * a_ta, gq);
-        st4_nt(p.g_eproj + (size_t)e * p.lde + c0, ((qi * kj) * gs) * d_ta);
+        score_bwd_edge(GS(e, hq), qi, kj, ld4_nt(p.eproj + (size_t)e * p.lde + c0), gq, p.g_eproj + (size_t)e * p.lde + c0);
     }
     st4(&red[slot * F + c0], gq);
     __syncthreads();
@@ -797,6 +727,8 @@ __device__ __forceinline__ void msg_bwd_merged_group_body(
         }
         cutp = group_sum(cutp, lps);
         if (lp == 0) cut_slice[e] = cutp;
+        // (slot_sums written out: the XR rl sums and the 8 head sums share the butterfly and leave for two arrays; through
+        //  a writer callback the kernels of this family came out with other register and spill counts)
         if (H <= 8 && lps >= KP) {
             multi_group_sum<KP>(vals, lps, lp);
             const int stride = lps / KP;
@@ -828,30 +760,31 @@ __device__ __forceinline__ void msg_bwd_merged_group_body(
 template <int LMAX, int LLO, int LHI, bool SCALAR, int FC = 0>
 __global__ __launch_bounds__(256) GN_WPE(GN_W_MSG_MRG_G) void msg_bwd_merged_group_kernel(const MsgBwdArgs p, float* __restrict__ ga_slice,
                                                                                         float* __restrict__ cut_slice) {
-    msg_bwd_merged_group_body<LMAX, LLO, LHI, SCALAR, FC>(p.x, p.v, p.ldxv, p.X_in, p.eproj, p.lde, p.a, p.rl, p.cut, p.g_h1,
-                                                           p.g_X1, p.dst, p.colptr, p.perm, p.g_eproj, p.g_x, p.g_v, p.g_X_out,
-                                                           p.g_rl, ga_slice, cut_slice, p.N, p.F, p.H);
+    msg_bwd_merged_group_body<LMAX, LLO, LHI, SCALAR, FC>(GN_MSGB_SOURCE_PTRS(p), ga_slice, cut_slice, p.N, p.F, p.H);
 }
 // the {3} group (155 VGPRs) under its own occupancy hint
 template <int LMAX, int LLO, int LHI, bool SCALAR, int FC = 0>
 __global__ __launch_bounds__(256) GN_WPE(GN_W_MSG_MRG_G3) void msg_bwd_merged_group3_kernel(const MsgBwdArgs p, float* __restrict__ ga_slice,
                                                                                         float* __restrict__ cut_slice) {
-    msg_bwd_merged_group_body<LMAX, LLO, LHI, SCALAR, FC>(p.x, p.v, p.ldxv, p.X_in, p.eproj, p.lde, p.a, p.rl, p.cut, p.g_h1,
-                                                           p.g_X1, p.dst, p.colptr, p.perm, p.g_eproj, p.g_x, p.g_v, p.g_X_out,
-                                                           p.g_rl, ga_slice, cut_slice, p.N, p.F, p.H);
+    msg_bwd_merged_group_body<LMAX, LLO, LHI, SCALAR, FC>(GN_MSGB_SOURCE_PTRS(p), ga_slice, cut_slice, p.N, p.F, p.H);
 }
+#undef GN_MSGB_SOURCE_PTRS
 
-// HTR backward per degree group (w = sum_l w_l: the degrees are independent)
+// HTR backward per degree group (w = sum_l w_l: the degrees are independent); lmax <= 2 is the one group {1 .. lmax}.
+// FIRST: the launch that also writes g_pre_t
 template <int LMAX, int LLO, int LHI, bool FIRST, int FC = 0>
-__global__ __launch_bounds__(256) GN_WPE(GN_W_HTR_TGT_G) void htr_bwd_target_group_kernel(
+__global__ __launch_bounds__(256) GN_WPE(GN_W_HTR_TGT) void htr_bwd_target_group_kernel(
     const float* __restrict__ gtp, const float* __restrict__ pre_t, const float* __restrict__ w,
     const float* __restrict__ EQ, const float* __restrict__ EK, const float* __restrict__ rl,
     const int* __restrict__ rowptr, const int* __restrict__ src, int N, int F_rt,
-    float* __restrict__ gEQ, float* __restrict__ g_rl, float* __restrict__ g_pre_t, int /* act: GN_ACT_SILU on this path, see gn_htr_backward */) {
+    float* __restrict__ gEQ, float* __restrict__ g_rl, float* __restrict__ g_pre_t) {
     constexpr int act = GN_ACT_SILU;
     constexpr int D = (LMAX + 1) * (LMAX + 1) - 1;
     constexpr int XR = (LHI + 1) * (LHI + 1) - LLO * LLO, M0 = LLO * LLO - 1;
-    constexpr int KP = XR <= 4 ? 4 : (XR <= 8 ? 8 : 16);
+    // w is read here and nowhere else after K7 wrote it: non-temporal at lmax <= 2 (step 7.555 / 7.534 -> 7.532 / 7.513 ms;
+    // the lmax 3 / 4 launches keep the ordinary load they were tuned with).  A non-temporal g_pre_t store measured nothing:
+    // the W_t^T product reads it next
+    constexpr bool W_NT = LMAX <= 2;
     constexpr int CH = XR < 9 ? XR : 9;
     __shared__ __attribute__((aligned(16))) float red[CH * 1024];
     const int F = FC ? FC : F_rt;
@@ -866,12 +799,11 @@ __global__ __launch_bounds__(256) GN_WPE(GN_W_HTR_TGT_G) void htr_bwd_target_gro
         float4 a_pt, d_pt;
         act_pair4(pte, act, a_pt, d_pt);
         const float4 gw = gte * a_pt;
-        if (FIRST) st4(g_pre_t + (size_t)e * F + c0, gte * ld4(w + (size_t)e * F + c0) * d_pt);
+        // t' = t + SiLU(pre_t) * w:  d/d pre_t, ready for the plain W_t^T product that follows
+        if (FIRST) st4(g_pre_t + (size_t)e * F + c0, gte * (W_NT ? ld4_nt(w + (size_t)e * F + c0) : ld4(w + (size_t)e * F + c0)) * d_pt);
         const float* kj = EK + (size_t)src[e] * D * F + c0;
         const float* re = rl + (size_t)e * D;
-        float part[KP];
-#pragma unroll
-        for (int m = 0; m < KP; ++m) part[m] = 0.f;
+        float part[XR];
 #pragma unroll
         for (int l = LLO; l <= LHI; ++l) {
             const int b0 = l * l - 1 - M0;
@@ -887,6 +819,7 @@ __global__ __launch_bounds__(256) GN_WPE(GN_W_HTR_TGT_G) void htr_bwd_target_gro
                 pb = fma4(r[mm], ek[mm], pb);
                 rr = fmaf(r[mm], r[mm], rr);
             }
+            // gw factored out of the per-row terms: u = -c gw pb, v = -c gw pa, s = 2 gw pa pb
             const float c = 2.0f - rr;
             const float4 u = gw * pb * (-c), v = gw * pa * (-c), s2 = gw * (pa * pb) * 2.0f;
 #pragma unroll
@@ -895,27 +828,18 @@ __global__ __launch_bounds__(256) GN_WPE(GN_W_HTR_TGT_G) void htr_bwd_target_gro
                 part[b0 + mm] = hsum4(fma4(r[mm], s2, fma4(v, ek[mm], u * eq[b0 + mm])));
             }
         }
-        if (lps >= KP) {
-            multi_group_sum<KP>(part, lps, lp);
-            const int stride = lps / KP;
-            if ((lp & (stride - 1)) == 0 && lp / stride < XR) g_rl[(size_t)e * D + M0 + lp / stride] = part[0];
-        } else {
-#pragma unroll
-            for (int m = 0; m < XR; ++m) {
-                const float sv = group_sum(part[m], lps);
-                if (lp == 0) g_rl[(size_t)e * D + M0 + m] = sv;
-            }
-        }
+        slot_sums(part, lps, lp, g_rl, (size_t)e * D + M0);
     }
     reduce_rows<XR>(acc, red, slot, c0, F, ns, [&](int row, float4 sv) { st4(gEQ + ((size_t)i * D + M0 + row) * F + c0, sv); });
 }
 
+// (not folded with htr_bwd_source_kernel: fma4(gw, eq + pa * (-c * r), acc) here, other bits there)
 template <int LMAX, int LLO, int LHI, int FC = 0>
 __global__ __launch_bounds__(256) GN_WPE(GN_W_HTR_SRC_G) void htr_bwd_source_group_kernel(
     const float* __restrict__ gtp, const float* __restrict__ pre_t,
     const float* __restrict__ EQ, const float* __restrict__ EK, const float* __restrict__ rl,
     const int* __restrict__ colptr, const int* __restrict__ perm, const int* __restrict__ dst, int N, int F_rt,
-    float* __restrict__ gEK, int /* act: GN_ACT_SILU on this path, see gn_htr_backward */) {
+    float* __restrict__ gEK) {
     constexpr int act = GN_ACT_SILU;
     constexpr int D = (LMAX + 1) * (LMAX + 1) - 1;
     constexpr int XR = (LHI + 1) * (LHI + 1) - LLO * LLO, M0 = LLO * LLO - 1;
@@ -1270,20 +1194,38 @@ static bool bwd_dim_ok_wide(int F) { return F >= 16 && F <= 1024 && gn::is_pow2(
         case 1: hipLaunchKernelGGL(gn::KERNEL<1>, grid, block, 0, st, __VA_ARGS__); break;             \
         case 2: hipLaunchKernelGGL(gn::KERNEL<2>, grid, block, 0, st, __VA_ARGS__); break;             \
         case 3: hipLaunchKernelGGL(gn::KERNEL<3>, grid, block, 0, st, __VA_ARGS__); break;             \
-        default: hipLaunchKernelGGL(gn::KERNEL<4>, grid, block, 0, st, __VA_ARGS__); break;            \
-    }
-
-#define GN_SWITCH_LMAX8(KERNEL, grid, block, st, ...)                                                  \
-    switch (lmax) {                                                                                    \
-        case 1: hipLaunchKernelGGL(gn::KERNEL<1>, grid, block, 0, st, __VA_ARGS__); break;             \
-        case 2: hipLaunchKernelGGL(gn::KERNEL<2>, grid, block, 0, st, __VA_ARGS__); break;             \
-        case 3: hipLaunchKernelGGL(gn::KERNEL<3>, grid, block, 0, st, __VA_ARGS__); break;             \
         case 4: hipLaunchKernelGGL(gn::KERNEL<4>, grid, block, 0, st, __VA_ARGS__); break;             \
         case 5: hipLaunchKernelGGL(gn::KERNEL<5>, grid, block, 0, st, __VA_ARGS__); break;             \
         case 6: hipLaunchKernelGGL(gn::KERNEL<6>, grid, block, 0, st, __VA_ARGS__); break;             \
         case 7: hipLaunchKernelGGL(gn::KERNEL<7>, grid, block, 0, st, __VA_ARGS__); break;             \
         default: hipLaunchKernelGGL(gn::KERNEL<8>, grid, block, 0, st, __VA_ARGS__); break;            \
     }
+
+// FC = 256: the instantiations with the width as a compile-time constant and wave-uniform slots (gn_common.h GN_SLOT_GEOMETRY)
+// By-target launches: {1 .. lmax} up to lmax 3, {1,2} + {3,4} at lmax 4; ONE by-source launch for all degrees (its accumulators
+// are the only rows it keeps).  Against {1,2},{3},{4} for both passes: nanotube (lmax 3) 300 -> 271 us per layer, lmax 4 273
+// either way (the gathered EQ / EK rows, 2 x 24 KiB per edge through L2, bound it, not the re-read [E,F] streams); own EQ
+// rows in LDS: no gain; a 3-wave hint: spills, 435 / 710 us.
+template <int FC>
+static void htr_backward_launch(const float* g_t_out, const float* pre_t, const float* w, const float* EQ, const float* EK,
+                                const float* rl, const int* rowptr, const int* src, const int* dst, const int* colptr,
+                                const int* perm, int N, int F, int lmax, float* gEQ, float* gEK, float* g_rl, float* g_pre_t,
+                                hipStream_t st) {
+    const dim3 grid(gn::xcd_grid(N)), block(256);
+#define GN_HTRB_T(L, LLO, LHI, FIRST)                                                                            \
+    hipLaunchKernelGGL((gn::htr_bwd_target_group_kernel<L, LLO, LHI, FIRST, FC>), grid, block, 0, st, g_t_out, pre_t, w, \
+                       EQ, EK, rl, rowptr, src, N, F, gEQ, g_rl, g_pre_t)
+#define GN_HTRB_S(...)                                                                                           \
+    hipLaunchKernelGGL((gn::__VA_ARGS__), grid, block, 0, st, g_t_out, pre_t, EQ, EK, rl, colptr, perm, dst, N, F, gEK)
+    switch (lmax) {
+        case 1: GN_HTRB_T(1, 1, 1, true); GN_HTRB_S(htr_bwd_source_kernel<1, FC>); break;
+        case 2: GN_HTRB_T(2, 1, 2, true); GN_HTRB_S(htr_bwd_source_kernel<2, FC>); break;
+        case 3: GN_HTRB_T(3, 1, 3, true); GN_HTRB_S(htr_bwd_source_group_kernel<3, 1, 3, FC>); break;
+        default: GN_HTRB_T(4, 1, 2, true); GN_HTRB_T(4, 3, 4, false); GN_HTRB_S(htr_bwd_source_group_kernel<4, 1, 4, FC>); break;
+    }
+#undef GN_HTRB_T
+#undef GN_HTRB_S
+}
 
 extern "C" int gn_htr_backward(const float* g_t_out, const float* pre_t, const float* w, const float* w_raw,
                                const float* EQ,
@@ -1302,35 +1244,8 @@ extern "C" int gn_htr_backward(const float* g_t_out, const float* pre_t, const f
     if (mode)
         return gn_htr_backward_general(g_t_out, pre_t, w, w_raw, EQ, EK, rl, rowptr, src, dst, colptr, perm, N, F, lmax,
                                        mode, gEQ, gEK, g_rl, g_pre_t, act, st);
-    const dim3 grid(gn::xcd_grid(N)), block(256);
-#define GN_HTRB_T(L, LLO, LHI, FIRST, FC)                                                                        \
-    hipLaunchKernelGGL((gn::htr_bwd_target_group_kernel<L, LLO, LHI, FIRST, FC>), grid, block, 0, st, g_t_out, pre_t, w, \
-                       EQ, EK, rl, rowptr, src, N, F, gEQ, g_rl, g_pre_t, act)
-#define GN_HTRB_S(L, LLO, LHI, FC)                                                                               \
-    hipLaunchKernelGGL((gn::htr_bwd_source_group_kernel<L, LLO, LHI, FC>), grid, block, 0, st, g_t_out, pre_t, EQ, EK, \
-                       rl, colptr, perm, dst, N, F, gEK, act)
-#define GN_HTRB(L, LLO, LHI, FIRST, FC) GN_HTRB_T(L, LLO, LHI, FIRST, FC); GN_HTRB_S(L, LLO, LHI, FC)
-    // F == 256: the instantiations with the width as a compile-time constant and wave-uniform slots (gn_common.h GN_SLOT_GEOMETRY)
-#define GN_HTRB_ALL(FC)                                                                                          \
-    if (lmax == 1) {                                                                                             \
-        hipLaunchKernelGGL((gn::htr_bwd_target_kernel<1, FC>), grid, block, 0, st, g_t_out, pre_t, w, EQ, EK, rl, rowptr, src, N, F, gEQ, g_rl, g_pre_t, act); \
-        hipLaunchKernelGGL((gn::htr_bwd_source_kernel<1, FC>), grid, block, 0, st, g_t_out, pre_t, EQ, EK, rl, colptr, perm, dst, N, F, gEK, act); \
-    } else if (lmax == 2) {                                                                                      \
-        hipLaunchKernelGGL((gn::htr_bwd_target_kernel<2, FC>), grid, block, 0, st, g_t_out, pre_t, w, EQ, EK, rl, rowptr, src, N, F, gEQ, g_rl, g_pre_t, act); \
-        hipLaunchKernelGGL((gn::htr_bwd_source_kernel<2, FC>), grid, block, 0, st, g_t_out, pre_t, EQ, EK, rl, colptr, perm, dst, N, F, gEK, act); \
-    } else if (lmax == 3) {                                                                                      \
-        if (GN_HTRB_TGT_MODE == 1) { GN_HTRB_T(3, 1, 3, true, FC); }                                             \
-        else { GN_HTRB_T(3, 1, 2, true, FC); GN_HTRB_T(3, 3, 3, false, FC); }                                    \
-        if (GN_HTRB_SRC_ONE) { GN_HTRB_S(3, 1, 3, FC); }                                                         \
-        else { GN_HTRB_S(3, 1, 2, FC); GN_HTRB_S(3, 3, 3, FC); }                                                 \
-    } else {                                                                                                     \
-        GN_HTRB_T(4, 1, 2, true, FC);                                                                            \
-        if (GN_HTRB_TGT_MODE == 1) { GN_HTRB_T(4, 3, 4, false, FC); }                                            \
-        else { GN_HTRB_T(4, 3, 3, false, FC); GN_HTRB_T(4, 4, 4, false, FC); }                                   \
-        if (GN_HTRB_SRC_ONE) { GN_HTRB_S(4, 1, 4, FC); }                                                         \
-        else { GN_HTRB_S(4, 1, 2, FC); GN_HTRB_S(4, 3, 3, FC); GN_HTRB_S(4, 4, 4, FC); }                         \
-    }
-    if (F == 256) { GN_HTRB_ALL(256) } else { GN_HTRB_ALL(0) }
+    if (F == 256) htr_backward_launch<256>(g_t_out, pre_t, w, EQ, EK, rl, rowptr, src, dst, colptr, perm, N, F, lmax, gEQ, gEK, g_rl, g_pre_t, st);
+    else htr_backward_launch<0>(g_t_out, pre_t, w, EQ, EK, rl, rowptr, src, dst, colptr, perm, N, F, lmax, gEQ, gEK, g_rl, g_pre_t, st);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }
@@ -1343,47 +1258,76 @@ static inline void gn_launch_msg_bwd_group(dim3 grid, dim3 block, hipStream_t st
     else
         hipLaunchKernelGGL((gn::msg_bwd_merged_group_kernel<L, LLO, LHI, SC, FC>), grid, block, 0, st, p, ga_slice, cut_slice);
 }
-// (lmax >= 3 with sep_dir and sep_tensor never comes here -- the degree groups take it -- so that form is not instantiated)
+// One (lmax, sep_dir, sep_tensor) shape outside the degree groups.  With the head-sum workspace (ga_parts) the merged form:
+// the by-source kernel with the per-edge work merged in (t_filter read once: PMC traffic of the family 1 148 -> 885 MB per
+// layer at lmax 2, 6.54 -> 6.40 ms per batch with three steps in flight), then the attention backward and g_k.  The first
+// interaction (X_in == NULL) takes it too, without the tensor-gate blocks (lmax 4 message backward 382 -> 373 us per layer).
+// Without the workspace the by-target / by-source pair; its X_in == NULL forms run at every lmax <= 4 in one launch each
+// (without the tensor-gate rows the register budget that forces the degree groups is gone; g_cut then uses ONE slice, the
+// caller zeroes the rest).  General launches at lmax >= 3 with sep_dir and sep_tensor never come here -- the degree groups
+// take them -- so neither form is instantiated for them (the by-source kernel of the pair would spill 94 VGPRs at lmax 4).
 template <int L, bool SD, bool ST, int FC>
-static inline void gn_launch_msg_bwd_merged(dim3 grid, dim3 block, hipStream_t st, const gn::MsgBwdArgs& p, float* ga_parts) {
-    if constexpr (!(L >= 3 && SD && ST))
-        hipLaunchKernelGGL((gn::msg_bwd_merged_kernel<L, SD, ST, FC>), grid, block, 0, st, p, ga_parts);
+static void gn_launch_msg_bwd(dim3 grid, dim3 block, hipStream_t st, const gn::MsgBwdArgs& p, float* ga_parts) {
+    constexpr bool GROUPED = L >= 3 && SD && ST;
+    if (ga_parts != nullptr) {
+        if (!p.X_in) hipLaunchKernelGGL((gn::msg_bwd_merged_first_kernel<L, SD, ST, FC>), grid, block, 0, st, p, ga_parts);
+        else if constexpr (!GROUPED) hipLaunchKernelGGL((gn::msg_bwd_merged_kernel<L, SD, ST, FC>), grid, block, 0, st, p, ga_parts);
+        hipLaunchKernelGGL(gn::attn_bwd_kernel<FC>, grid, block, 0, st, p, ga_parts, 1, (size_t)0);
+        hipLaunchKernelGGL(gn::msg_bwd_gk_kernel<FC>, grid, block, 0, st, p);
+    } else if (!p.X_in) {
+        hipLaunchKernelGGL((gn::msg_bwd_target_kernel<L, SD, ST, true, FC>), grid, block, 0, st, p);
+        hipLaunchKernelGGL((gn::msg_bwd_source_kernel<L, SD, ST, true, FC>), grid, block, 0, st, p);
+    } else if constexpr (!GROUPED) {
+        hipLaunchKernelGGL((gn::msg_bwd_target_kernel<L, SD, ST>), grid, block, 0, st, p);       // (run-time width at every F)
+        hipLaunchKernelGGL((gn::msg_bwd_source_kernel<L, SD, ST>), grid, block, 0, st, p);
+    }
 }
-// X_in == NULL: the zero-X_in instantiations (one target + one source launch at every lmax <= 4: without the tensor-gate
-// rows the register budget that forces the degree groups is gone; g_cut then uses ONE slice, the caller zeroes the rest)
-#define GN_MSGB_LAUNCH_FC(L, SD, ST, FC)                                                                 \
-    do {                                                                                                  \
-        if (!X_in) {                                                                                      \
-            if (GN_MSGB_MERGED_FIRST && ga_parts != nullptr) {   /* first interaction: merged form without the tensor-gate blocks */ \
-                hipLaunchKernelGGL((gn::msg_bwd_merged_first_kernel<L, SD, ST, FC>), grid, block, 0, st, p, ga_parts); \
-                hipLaunchKernelGGL(gn::attn_bwd_kernel<FC>, grid, block, 0, st, p, ga_parts, 1, (size_t)0); \
-                hipLaunchKernelGGL(gn::msg_bwd_gk_kernel<FC>, grid, block, 0, st, p);                     \
-                break;                                                                                    \
-            }                                                                                             \
-            hipLaunchKernelGGL((gn::msg_bwd_target_kernel<L, SD, ST, true, FC>), grid, block, 0, st, p);  \
-            hipLaunchKernelGGL((gn::msg_bwd_source_kernel<L, SD, ST, true, FC>), grid, block, 0, st, p);  \
-            break;                                                                                        \
-        }                                                                                                 \
-        if (GN_MSGB_MERGED && ga_parts != nullptr) {     /* general launches: t_filter read once (gn_tune.h) */ \
-            gn_launch_msg_bwd_merged<L, SD, ST, FC>(grid, block, st, p, ga_parts);                        \
-            hipLaunchKernelGGL(gn::attn_bwd_kernel<FC>, grid, block, 0, st, p, ga_parts, 1, (size_t)0);   \
-            hipLaunchKernelGGL(gn::msg_bwd_gk_kernel<FC>, grid, block, 0, st, p);                         \
-            break;                                                                                        \
-        }                                                                                                 \
-        hipLaunchKernelGGL((gn::msg_bwd_target_kernel<L, SD, ST>), grid, block, 0, st, p);                \
-        hipLaunchKernelGGL((gn::msg_bwd_source_kernel<L, SD, ST>), grid, block, 0, st, p);                \
-    } while (0)
-#define GN_MSGB_LAUNCH(L, SD, ST) GN_MSGB_LAUNCH_FC(L, SD, ST, 0)
-// the reference's defaults (sep_dir, sep_tensor) at F = 256: the compile-time-width instantiations
-#define GN_MSGB_LAUNCH_DEFAULT(L)                                                                        \
-    do {                                                                                                  \
-        if (F == 256) GN_MSGB_LAUNCH_FC(L, true, true, 256); else GN_MSGB_LAUNCH_FC(L, true, true, 0);    \
-    } while (0)
 
 extern "C" int gn_message_backward_groups(int lmax_arg, int sep_dir, int sep_tensor, int act) {
     const int lmax = lmax_arg & 0xff;
     if (gn_use_highl(lmax_arg) || act != GN_ACT_SILU) return 1;      // degree-sliced kernels (gn_highl.hip): one slice
     return (lmax >= 3 && sep_dir && sep_tensor) ? lmax - 1 : 1;
+}
+
+// FC = 256: the compile-time-width instantiations; the register-tiled shapes have them at lmax 1 and for the reference's
+// defaults (sep_dir, sep_tensor) only, the other shapes run the run-time-width kernels at every F
+template <int FC>
+static void message_backward_launch(const gn::MsgBwdArgs& p, int lmax, int sep_dir, int sep_tensor, bool groups, float* ga_parts,
+                                    long E, hipStream_t st) {
+    const dim3 grid(gn::xcd_grid(p.N)), block(256);
+    if (groups) {
+        // by-source group kernels with the per-edge work merged in (t_filter read once; head sums and cut slices per group)
+        // -> attention backward over the summed head gradients -> g_k
+        const size_t gs = (size_t)E * p.H;
+#define GN_MSGB_M(L, LLO, LHI, SC, G)                                                                        \
+    gn_launch_msg_bwd_group<L, LLO, LHI, SC, FC>(grid, block, st, p, ga_parts + (size_t)(G) * gs, p.g_cut + (size_t)(G) * E)
+        if (lmax == 3) { GN_MSGB_M(3, 1, 2, true, 0); GN_MSGB_M(3, 3, 3, false, 1); }
+        else { GN_MSGB_M(4, 1, 2, true, 0); GN_MSGB_M(4, 3, 3, false, 1); GN_MSGB_M(4, 4, 4, false, 2); }
+#undef GN_MSGB_M
+        hipLaunchKernelGGL(gn::attn_bwd_kernel<FC>, grid, block, 0, st, p, ga_parts, lmax - 1, gs);
+        hipLaunchKernelGGL(gn::msg_bwd_gk_kernel<FC>, grid, block, 0, st, p);
+        return;
+    }
+#define GN_MSGB_CASE(L, SD, ST, W) \
+    case (L) * 4 + (SD ? 2 : 0) + (ST ? 1 : 0): gn_launch_msg_bwd<L, SD, ST, W>(grid, block, st, p, ga_parts); break
+    switch (lmax * 4 + (sep_dir ? 2 : 0) + (sep_tensor ? 1 : 0)) {
+        case 4: case 5: case 6: case 7:              // (lmax 1 is one degree: sep_dir / sep_tensor change nothing)
+            gn_launch_msg_bwd<1, false, false, FC>(grid, block, st, p, ga_parts);
+            break;
+        GN_MSGB_CASE(2, false, false, 0);
+        GN_MSGB_CASE(2, false, true, 0);
+        GN_MSGB_CASE(2, true, false, 0);
+        GN_MSGB_CASE(2, true, true, FC);
+        GN_MSGB_CASE(3, false, false, 0);
+        GN_MSGB_CASE(3, false, true, 0);
+        GN_MSGB_CASE(3, true, false, 0);
+        GN_MSGB_CASE(3, true, true, FC);
+        GN_MSGB_CASE(4, false, false, 0);
+        GN_MSGB_CASE(4, false, true, 0);
+        GN_MSGB_CASE(4, true, false, 0);
+        default: gn_launch_msg_bwd<4, true, true, FC>(grid, block, st, p, ga_parts); break;
+    }
+#undef GN_MSGB_CASE
 }
 
 static int message_backward(
@@ -1406,43 +1350,12 @@ static int message_backward(
                      rowptr, src, dst, colptr, perm, g_eproj, g_s, g_nproj, ldn, g_x, g_v, g_X_out, g_rl, g_cut,
                      N, F, H, (float)(1.0 / sqrt((double)F)), act, (lmax_arg & GN_LMAX_MEAN) ? 1 : 0, amax ? ga_parts : nullptr, a_soft};
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(gn::xcd_grid(N)), block(256);
     // (F > 256: the degree-sliced kernels; g_rl / g_cut come as F / 256 partial slices, the caller sized them so)
     if (gn_use_highl(lmax_arg) || F > 256 || act != GN_ACT_SILU) return gn_highl_message_backward(p, lmax, sep_dir, sep_tensor, st);
-    if (X_in && gn_message_backward_groups(lmax_arg, sep_dir, sep_tensor, act) > 1) {
-        if (ga_parts == nullptr || E <= 0) return GN_ERR_BAD_ARG;
-        const size_t gs = (size_t)E * H;
-#define GN_MSGB_M(L, LLO, LHI, SC, G, FC)                                                                    \
-    gn_launch_msg_bwd_group<L, LLO, LHI, SC, FC>(grid, block, st, p, ga_parts + (size_t)(G) * gs, g_cut + (size_t)(G) * E)
-        // by-source group kernels with the per-edge work merged in (t_filter read once; head sums and cut slices per group)
-        // -> attention backward over the summed head gradients -> g_k
-#define GN_MSGB_GROUPS(FC)                                                                                       \
-        if (lmax == 3) { GN_MSGB_M(3, 1, 2, true, 0, FC); GN_MSGB_M(3, 3, 3, false, 1, FC); }                    \
-        else { GN_MSGB_M(4, 1, 2, true, 0, FC); GN_MSGB_M(4, 3, 3, false, 1, FC); GN_MSGB_M(4, 4, 4, false, 2, FC); } \
-        hipLaunchKernelGGL(gn::attn_bwd_kernel<FC>, grid, block, 0, st, p, ga_parts, lmax - 1, gs);              \
-        hipLaunchKernelGGL(gn::msg_bwd_gk_kernel<FC>, grid, block, 0, st, p);
-        if (F == 256) { GN_MSGB_GROUPS(256) } else { GN_MSGB_GROUPS(0) }
-        GN_LAUNCH_CHECK();
-        return GN_OK;
-    }
-    const int key = lmax * 4 + (sep_dir ? 2 : 0) + (sep_tensor ? 1 : 0);
-    switch (key) {
-        case 4: case 5: case 6: case 7:
-            if (F == 256) GN_MSGB_LAUNCH_FC(1, false, false, 256); else GN_MSGB_LAUNCH(1, false, false);
-            break;
-        case 8: GN_MSGB_LAUNCH(2, false, false); break;
-        case 9: GN_MSGB_LAUNCH(2, false, true); break;
-        case 10: GN_MSGB_LAUNCH(2, true, false); break;
-        case 11: GN_MSGB_LAUNCH_DEFAULT(2); break;
-        case 12: GN_MSGB_LAUNCH(3, false, false); break;
-        case 13: GN_MSGB_LAUNCH(3, false, true); break;
-        case 14: GN_MSGB_LAUNCH(3, true, false); break;
-        case 15: GN_MSGB_LAUNCH_DEFAULT(3); break;
-        case 16: GN_MSGB_LAUNCH(4, false, false); break;
-        case 17: GN_MSGB_LAUNCH(4, false, true); break;
-        case 18: GN_MSGB_LAUNCH(4, true, false); break;
-        default: GN_MSGB_LAUNCH_DEFAULT(4); break;
-    }
+    const bool groups = X_in && gn_message_backward_groups(lmax_arg, sep_dir, sep_tensor, act) > 1;
+    if (groups && (ga_parts == nullptr || E <= 0)) return GN_ERR_BAD_ARG;
+    if (F == 256) message_backward_launch<256>(p, lmax, sep_dir, sep_tensor, groups, ga_parts, E, st);
+    else message_backward_launch<0>(p, lmax, sep_dir, sep_tensor, groups, ga_parts, E, st);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }
@@ -1547,7 +1460,7 @@ extern "C" int gn_edge_geometry_backward(const float* edge_vec, const float* edg
     if (E == 0) return GN_OK;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((E + 127) / 128), block(128);
-    GN_SWITCH_LMAX8(edge_geometry_bwd_kernel, grid, block, st, edge_vec, edge_diff, src, dst, E, R, basis, means, betas,
+    GN_SWITCH_LMAX(edge_geometry_bwd_kernel, grid, block, st, edge_vec, edge_diff, src, dst, E, R, basis, means, betas,
                    cutoff, 5.0f / cutoff, g_rl, n_rl, g_cut, n_cut, g_phi, g_vec, g_diff);
     GN_LAUNCH_CHECK();
     return GN_OK;

@@ -257,7 +257,9 @@ __global__ __launch_bounds__(256) void hl_msg_bwd_target_kernel(const MsgBwdArgs
             }
         }
         slot_sum_store(cutp, lps, lp, p.g_cut + e, E_all, valid);
-        // head sums (same staging as msg_bwd_target_body; a slot within one wave: wave-ordered LDS accesses, no barrier)
+        // head sums: the staging of slot_head_sums (gn_backward.hip), written out here because M is a run-time value, the row
+        // is filled inside the block loop above and wide slots need the two barriers (a slot within one wave: wave-ordered
+        // LDS accesses, no barrier)
         if (wide) __syncthreads();
         {
             const int rpl = lps / H, hh = lp / rpl, part = lp - hh * rpl;

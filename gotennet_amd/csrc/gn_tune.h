@@ -21,13 +21,10 @@
 #define GN_W_MSG_SRC 2     // without it the scheduler serialises every row load to reach 3 waves/SIMD: 393 -> 327 us (both passes)
 #endif
 #ifndef GN_W_HTR_TGT
-#define GN_W_HTR_TGT 0     // 2, 3: within noise; 4: 140 -> 268 us
+#define GN_W_HTR_TGT 0     // htr_bwd_target_group_kernel, every degree group.  2, 3: within noise; 4: 140 -> 268 us
 #endif
 #ifndef GN_W_HTR_SRC
 #define GN_W_HTR_SRC 0
-#endif
-#ifndef GN_W_HTR_TGT_G
-#define GN_W_HTR_TGT_G 0
 #endif
 #ifndef GN_W_HTR_SRC_G
 #define GN_W_HTR_SRC_G 0
@@ -54,19 +51,9 @@
                            // cost nothing, the kernel sits at 2 waves/SIMD on registers)
 #endif
 
-#ifndef GN_MSGB_MERGED
-#define GN_MSGB_MERGED 1   // message backward at lmax <= 2 (general launches): 1 = by-source kernel with the per-edge work merged in
-#endif                     // (t_filter read once) + attention backward + g_k; 0 = the by-target / by-source pair
-#ifndef GN_MSGB_MERGED_FIRST
-#define GN_MSGB_MERGED_FIRST 1   // the first interaction (X_in == 0) through the merged kernel too (scalar + direction-gate blocks only)
-#endif
-#ifndef GN_HTRB_SRC_ONE
-#define GN_HTRB_SRC_ONE 1  // HTR backward at lmax 3 / 4: ONE by-source launch for all degrees (its accumulators are the only rows it keeps)
-#endif
-#ifndef GN_HTRB_TGT_MODE
-#define GN_HTRB_TGT_MODE 1 // ... by-target launches: 0 = {1,2},{3},{4}; 1 = {1,2,3} at lmax 3, {1,2},{3,4} at lmax 4.  Nanotube (lmax 3)
-#endif                     // 300 -> 271 us per layer with both, lmax 4 273 either way (the gathered EQ / EK rows, 2 x 24 KiB per edge
-                           // through L2, bound it, not the re-read [E,F] streams); own EQ rows in LDS: no gain; a 3-wave hint: spills, 435 / 710 us
+// (settled, the switches are gone and the findings stand at the launch sites in gn_backward.hip: message backward runs the
+// merged by-source kernel + attention backward + g_k whenever the caller gives the head-sum workspace, the first interaction
+// included; HTR backward at lmax 3 / 4 runs ONE by-source launch and the by-target groups {1,2,3} / {1,2},{3,4}.)
 #ifndef GN_W_MSG_MRG_G
 #define GN_W_MSG_MRG_G 2   // degree-group kernels {scalar,1,2} and {4} ...
 #endif

@@ -254,7 +254,7 @@ def test_parameter_gradients_match_masked_oracle(monkeypatch, name):
 
 
 # ---------------------------------------------------------------------------------------------------- 5. strip overflow
-def _hub_case(F):
+def _hub_case(F, lmax=2):
     """A hand-made graph: target 0 with in-degree 300 (300 * 8 heads exceeds the wave strip's 512 floats, the softmax
     workgroup kernel's 2048 and the backward's GS_CAP = 2048), four ordinary atoms, one atom without incoming edges."""
     import gotennet_amd
@@ -276,7 +276,7 @@ def _hub_case(F):
     ei = ei[:, torch.sort(ei[1], stable=True).indices].contiguous()
     assert int((ei[1] == 0).sum()) == 300 and int((ei[1] == 300).sum()) == 0
     torch.manual_seed(F + 1)
-    kw = dict(n_atom_basis=F, n_interactions=2, n_rbf=16, num_heads=8, scale_edge=True, lmax=2, sep_dir=True, sep_tensor=True)
+    kw = dict(n_atom_basis=F, n_interactions=2, n_rbf=16, num_heads=8, scale_edge=True, lmax=lmax, sep_dir=True, sep_tensor=True)
     net = gotennet_amd.GotenNet(cutoff_fn=gotennet_amd.CosineCutoff(5.0), **kw)
     head = Atomwise(n_in=F, n_hidden=16, property="property", activation="silu")
     with torch.no_grad():
@@ -317,6 +317,29 @@ def test_hub_target_beyond_the_strips(monkeypatch, F):
             rel_err(f.cpu(), -g_ref))
     print(f"hub F={F}: h {errs[0]:.2e} X {errs[1]:.2e} energy {errs[2]:.2e} forces {errs[3]:.2e}")
     assert max(errs) < TOL
+
+
+@pytest.mark.parametrize("lmax,pair", [(2, True), (3, False)])
+def test_hub_target_head_gradients_in_global_memory(monkeypatch, lmax, pair):
+    """Eval mode, no dropout: the hub's 300 * 8 head gradients exceed GS_CAP = 2048, so the softmax / scores backward of
+    that target works on the global g_s rows instead of LDS -- in the by-target kernel of the by-target / by-source pair
+    (lmax 2, no head-sum workspace) and in attn_bwd_kernel over the two head-sum slices of the degree groups (lmax 3)."""
+    from gotennet_amd import engine
+    from oracle import gotennet_oracle as orc
+    monkeypatch.setattr(engine, "MSG_BWD_PAIR", pair)
+    cfg, sd, head_sd, z, pos, ei, net, head = _hub_case(32, lmax)
+    net = _set_dropout(net.cuda().requires_grad_(False), 0.0, train=False)
+    head = head.cuda().eval().requires_grad_(False)
+    t = dict(z=z, pos=pos, batch=torch.zeros(z.shape[0], dtype=torch.int64), edge_index=ei)
+    e, f = _gpu_forces(net, head, t)
+    p64 = pos.double().requires_grad_(True)
+    w64, vec64 = _edges_from_pos(p64, ei)
+    h_ref, _ = orc.gotennet_forward(_d64(sd), cfg, z, ei, w64, vec64)
+    e_ref = orc.atomwise_energy(_d64(head_sd), h_ref, t["batch"], 1, "silu", z=z)
+    (g_ref,) = torch.autograd.grad(e_ref.sum(), p64)
+    ee, ef = rel_err(e.cpu(), e_ref.detach()), rel_err(f.cpu(), -g_ref)
+    print(f"hub lmax={lmax} pair={pair}: energy {ee:.2e} forces {ef:.2e}")
+    assert ee < TOL and ef < TOL
 
 
 # ---------------------------------------------------------------------------------------------------- 6. unchanged paths

@@ -2,7 +2,7 @@
 # Occupancy-hint sweep for the gather kernels (gn_tune.h).  Stage 1 (here, CPU): build one library per
 # (kernel, waves/SIMD) pair.  Stage 2 (GPU box): `bash tools/tune_sweep.sh run` benches each library.
 cd "$(dirname "$0")/.."
-VARIANTS="${VARIANTS:-MSG_SRC=1 MSG_SRC=2 MSG_SRC=3 MSG_SRC=4 MSG_TGT=3 MSG_TGT=4 HTR_TGT=2 HTR_TGT=3 HTR_TGT=4 HTR_SRC=2 HTR_SRC=3 HTR_EDGE=2 HTR_EDGE=4 ATTN=2 ATTN=4 MSG_SRC_G=2 MSG_SRC_G=3 MSG_TGT_G=2 MSG_TGT_G=3 HTR_TGT_G=2 HTR_TGT_G=3 HTR_SRC_G=2 HTR_SRC_G=3 K6=3 K6_G=3}"
+VARIANTS="${VARIANTS:-MSG_SRC=1 MSG_SRC=2 MSG_SRC=3 MSG_SRC=4 MSG_TGT=3 MSG_TGT=4 HTR_TGT=2 HTR_TGT=3 HTR_TGT=4 HTR_SRC=2 HTR_SRC=3 HTR_EDGE=2 HTR_EDGE=4 ATTN=2 ATTN=4 MSG_SRC_G=2 MSG_SRC_G=3 MSG_TGT_G=2 MSG_TGT_G=3 HTR_SRC_G=2 HTR_SRC_G=3 K6=3 K6_G=3}"
 if [ "$1" != "run" ]; then
   mkdir -p gotennet_amd/sweep
   build_one() {
