@@ -99,6 +99,10 @@ SIGNATURES = {
     "gn_geb_gate": [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P],
     "gn_dipole_reduce": [_P, _I, _P, _I, _P, _P, _I, _F, _F, _I, _I, _P, _P, _P],
     "gn_ese_reduce": [_P, _P, _P, _P, _I, _P, _I, _P, _P],
+    "gn_geb_gate_backward": [_P, _I, _P, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P],
+    "gn_geb_context_backward": [_P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P],
+    "gn_dipole_reduce_backward": [_P, _P, _P, _I, _P, _I, _P, _P, _I, _F, _F, _I, _I, _P, _I, _P, _I, _P],
+    "gn_ese_reduce_backward": [_P, _P, _P, _P, _I, _P, _I, _P, _P],
     "gn_radius_count": [_P, _P, _I, _F, _I, _P, _P],
     "gn_radius_fill": [_P, _P, _I, _F, _I, _P, C.c_int64, _P, _P, _P, _P],
     "gn_weight_grad_workspace": [_P, _I],

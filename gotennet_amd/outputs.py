@@ -351,46 +351,56 @@ class _AtomwiseParamFn(torch.autograd.Function):
         from .gotennet import refuse_second_order
         refuse_second_order("Atomwise.parameter_grads")
         head, mol_ptr, h, tape, acts, layers, c, params = ctx.state
-        pres, last_in, atom_scale = tape
-        N, Hd = last_in.shape
+        _, last_in, atom_scale = tape
         n_out = getattr(head, "n_out", 1)
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=h.device)
         u = ge.reshape(-1, n_out).to(torch.float32)
-        if head.aggregation_mode is not None and u.shape[0] != N:
+        if head.aggregation_mode is not None and u.shape[0] != last_in.shape[0]:
             mp = mol_ptr.long()
             u = torch.repeat_interleave(u, mp[1:] - mp[:-1], dim=0)
         if atom_scale is not None:
             u = u * atom_scale.unsqueeze(1)
         scales = c["scales"] if n_out > 1 else [c["scale"]]
-        U = (u * torch.tensor(scales, dtype=torch.float32, device=h.device)).contiguous()
         weights = not ctx.gn_positions_only          # False inside positions_only(): dL/dh alone
-        grads = {id(d.weight): torch.empty_like(d.weight) for d in layers}
-        grads.update({id(d.bias): torch.empty_like(d.bias) for d in layers})
-        a_last = acts[-1] if acts else h
-        probs = [dict(dY=U, ldy=n_out, A=a_last, lda=Hd, dW=grads[id(layers[-1].weight)], db=grads[id(layers[-1].bias)],
-                      rows=N, nout=n_out, K=Hd)]
-        # g = dL/d pre_last (dL/dh without hidden layers): sum_o u^o scale_o W_o act'(pre_last)
-        act_last = head.act_kind if pres else 11
-        g, part = new(N, Hd), new(N, Hd)
-        for o in range(n_out):
-            w_o = c["w_rows"][o] if n_out > 1 else c["w"][-1]
-            call("gn_head_grad", ptr(last_in), ptr(w_o), scales[o], ptr(u[:, o].contiguous()), N, Hd,
-                 ptr(g if o == 0 else part), act_last, engine._stream())
-            if o:
-                g.add_(part)
-        for k in range(len(pres) - 1, -1, -1):       # g = dL/d pre_k
-            d = layers[k]
-            probs.append(dict(dY=g, ldy=d.out_features, A=acts[k - 1] if k > 0 else h, lda=d.in_features,
-                              dW=grads[id(d.weight)], db=grads[id(d.bias)], rows=N, nout=d.out_features, K=d.in_features))
-            gi = new(N, d.in_features)
-            engine.gemm(g, d.out_features, c["wt"][k], None, gi, d.in_features, N, d.in_features, d.out_features,
-                        dgate=pres[k - 1] if k > 0 else None, kind=head.act_kind)
-            g = gi
-        if not weights:
-            return (g if ctx.needs_input_grad[0] else None, None, None, None, None, *([None] * len(params)))
-        engine.weight_grad_group(probs)
-        pg = [grads.get(id(p)) if ctx.needs_input_grad[5 + i] else None for i, p in enumerate(params)]
+        g, grads = _out_net_backward(head, h, tape, acts, layers, c, u, scales, weights)
+        pg = [grads.get(id(p)) if (weights and ctx.needs_input_grad[5 + i]) else None for i, p in enumerate(params)]
         return (g if ctx.needs_input_grad[0] else None, None, None, None, None, *pg)
+
+
+def _out_net_backward(head, h, tape, acts, layers, c, u, scales, weights: bool = True):
+    """Backward of the head's out_net (SchnetMLP) from the per-atom upstream gradient ``u`` [N, n_out] of its RAW outputs
+    times ``scales`` -> (dL/dh, {id(parameter): gradient}); the dict is empty without ``weights``.  Shared by
+    ``_AtomwiseParamFn`` and ``_ESEParamFn``."""
+    pres, last_in, _ = tape
+    N, Hd = last_in.shape
+    n_out = getattr(head, "n_out", 1)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=h.device)
+    U = (u * torch.tensor(scales, dtype=torch.float32, device=h.device)).contiguous()
+    grads = {id(d.weight): torch.empty_like(d.weight) for d in layers}
+    grads.update({id(d.bias): torch.empty_like(d.bias) for d in layers})
+    a_last = acts[-1] if acts else h
+    probs = [dict(dY=U, ldy=n_out, A=a_last, lda=Hd, dW=grads[id(layers[-1].weight)], db=grads[id(layers[-1].bias)],
+                  rows=N, nout=n_out, K=Hd)]
+    # g = dL/d pre_last (dL/dh without hidden layers): sum_o u^o scale_o W_o act'(pre_last)
+    act_last = head.act_kind if pres else 11
+    g, part = new(N, Hd), new(N, Hd)
+    for o in range(n_out):
+        w_o = c["w_rows"][o] if n_out > 1 else c["w"][-1]
+        call("gn_head_grad", ptr(last_in), ptr(w_o), scales[o], ptr(u[:, o].contiguous()), N, Hd,
+             ptr(g if o == 0 else part), act_last, engine._stream())
+        if o:
+            g.add_(part)
+    for k in range(len(pres) - 1, -1, -1):       # g = dL/d pre_k
+        d = layers[k]
+        probs.append(dict(dY=g, ldy=d.out_features, A=acts[k - 1] if k > 0 else h, lda=d.in_features,
+                          dW=grads[id(d.weight)], db=grads[id(d.bias)], rows=N, nout=d.out_features, K=d.in_features))
+        gi = new(N, d.in_features)
+        engine.gemm(g, d.out_features, c["wt"][k], None, gi, d.in_features, N, d.in_features, d.out_features,
+                    dgate=pres[k - 1] if k > 0 else None, kind=head.act_kind)
+        g = gi
+    if not weights:
+        return g, {}
+    engine.weight_grad_group(probs)
+    return g, grads
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -402,7 +412,8 @@ def _pad4(n: int) -> int:
 class GatedEquivariantBlock(nn.Module):
     """Reference outputs.py:24-93 (state_dict keys ``mix_vectors.weight``, ``scalar_net.{0,1}.{weight,bias}``).
     ``forward(scalars [N, n_sin], vectors [N, 3, n_vin]) -> (s_out [N, n_sout], v_out [N, 3, n_vout])``; ``vectors`` may be
-    the ``X[:, :3, :]`` view of the [N, D, F] vector representation.  Inference only."""
+    the ``X[:, :3, :]`` view of the [N, D, F] vector representation (its gradient then has exact zeros in rows 3 and above).
+    ``parameter_grads = True`` makes the block trainable (first order)."""
 
     def __init__(self, n_sin: int, n_vin: int, n_sout: int, n_vout: int, n_hidden: int, activation=F.silu,
                  sactivation=None):
@@ -416,6 +427,9 @@ class GatedEquivariantBlock(nn.Module):
         self.scalar_net = nn.Sequential(Dense(n_sin + n_vout, n_hidden, activation=resolve_activation(activation)),
                                         Dense(n_hidden, n_sout + n_vout, activation=None))
         self.sactivation = resolve_activation(sactivation) if sactivation is not None else None
+        #: True: with grad mode on and an input or parameter requiring grad, ``forward`` is differentiable (first order):
+        #: dL/dscalars, dL/dvectors and d loss / d parameter; a backward with create_graph=True is refused
+        self.parameter_grads = False
 
     def invalidate_packed(self):
         self._cache = None
@@ -452,31 +466,109 @@ class GatedEquivariantBlock(nn.Module):
             self._cache = c
         return c
 
+    def _packed_t(self):
+        """``_packed()`` plus the transposed (padded) weights the backward's input-gradient products read."""
+        c = self._packed()
+        if "w1t" not in c:
+            c.update(w1t=c["w1"].t().contiguous(), w0t=c["w0"].t().contiguous(), wmixt=c["wmix"].t().contiguous())
+        return c
+
+    def _run(self, c, scalars: torch.Tensor, vectors: torch.Tensor, save: bool = False):
+        """The block's launches on detached fp32 inputs -> (s_out, v_out, saved); ``saved`` (``save``: what the backward
+        reads, with the hidden layer's pre-activation as one more output of its product) is None otherwise."""
+        N = scalars.shape[0]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=scalars.device)
+        pv, kc, po, nh = c["pv"], c["kc"], c["po"], self.n_hidden
+        vmix, ctx, hid, x = new(N * 3, 2 * pv), new(N, kc), new(N, nh), new(N, po)
+        pre0 = new(N, nh) if save else None
+        engine.gemm(vectors, self.n_vin, c["wmix"], None, vmix, 2 * pv, N * 3, 2 * pv, self.n_vin, kind=self.act_kind)
+        call("gn_geb_context", ptr(scalars), scalars.stride(0), self.n_sin, ptr(vmix), 2 * pv, self.n_vout, N, ptr(ctx), kc,
+             engine._stream())
+        engine.gemm(ctx, kc, c["w0"], c["b0"], hid, nh, N, nh, kc, act=(0, nh), pre_out=pre0, kind=self.act_kind)
+        engine.gemm(hid, nh, c["w1"], c["b1"], x, po, N, po, nh, kind=self.act_kind)
+        s_out, v_out = new(N, self.n_sout), new(N, 3, self.n_vout)
+        call("gn_geb_gate", ptr(x), po, self.n_sout, self.n_vout, ptr(vmix), 2 * pv, pv, N, self.sact_kind,
+             ptr(s_out), self.n_sout, ptr(v_out), self.n_vout, engine._stream())
+        return s_out, v_out, ((vectors, vmix, ctx, pre0, hid, x) if save else None)
+
+    def _params(self):
+        return [self.mix_vectors.weight, self.scalar_net[0].weight, self.scalar_net[0].bias,
+                self.scalar_net[1].weight, self.scalar_net[1].bias]
+
     def forward(self, scalars: torch.Tensor, vectors: torch.Tensor):
         if not scalars.is_cuda:
             raise GotenNetHipError("gotennet_amd.outputs.GatedEquivariantBlock runs on a ROCm device only")
-        c = self._packed()
-        N = scalars.shape[0]
         if vectors.shape[1] != 3 or vectors.shape[2] != self.n_vin:
             raise ValueError(f"vectors must be [N, 3, {self.n_vin}]")
+        if self.parameter_grads and torch.is_grad_enabled():
+            params = self._params()
+            if scalars.requires_grad or vectors.requires_grad or any(p.requires_grad for p in params):
+                return _GatedBlockParamFn.apply(scalars, vectors, self, *params)
         # the X[:, :3, :] view of [N, D, F] is gathered into [N, 3, F] by a device copy (index plumbing: the GEMM's row map
         # addresses input AND output rows, and the mixing product's output is dense)
         vectors = vectors.detach().to(torch.float32).contiguous()
         scalars = scalars.detach().to(torch.float32)
         if scalars.stride(-1) != 1:
             scalars = scalars.contiguous()
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=scalars.device)
-        pv, kc, po, nh = c["pv"], c["kc"], c["po"], self.n_hidden
-        vmix, ctx, hid, x = new(N * 3, 2 * pv), new(N, kc), new(N, nh), new(N, po)
-        engine.gemm(vectors, self.n_vin, c["wmix"], None, vmix, 2 * pv, N * 3, 2 * pv, self.n_vin, kind=self.act_kind)
-        call("gn_geb_context", ptr(scalars), scalars.stride(0), self.n_sin, ptr(vmix), 2 * pv, self.n_vout, N, ptr(ctx), kc,
-             engine._stream())
-        engine.gemm(ctx, kc, c["w0"], c["b0"], hid, nh, N, nh, kc, act=(0, nh), kind=self.act_kind)
-        engine.gemm(hid, nh, c["w1"], c["b1"], x, po, N, po, nh, kind=self.act_kind)
-        s_out, v_out = new(N, self.n_sout), new(N, 3, self.n_vout)
-        call("gn_geb_gate", ptr(x), po, self.n_sout, self.n_vout, ptr(vmix), 2 * pv, pv, N, self.sact_kind,
-             ptr(s_out), self.n_sout, ptr(v_out), self.n_vout, engine._stream())
+        s_out, v_out, _ = self._run(self._packed(), scalars, vectors)
         return s_out, v_out
+
+
+class _GatedBlockParamFn(torch.autograd.Function):
+    """(scalars, vectors, *parameters) -> (s_out, v_out) with parameter gradients (``GatedEquivariantBlock.parameter_grads``).
+    With the notation of the forward (vmix = [V | W], ctx = [s | ||V||], pre0 = ctx W0^T + b0, hid = act(pre0),
+    x = hid W1^T + b1 = [s_raw | gate]): the gate adjoint gives g_x and the W half of g_vmix; dW1, db1 from (g_x, hid);
+    g_pre0 = (g_x W1) act'(pre0); dW0, db0 from (g_pre0, ctx); g_ctx = g_pre0 W0; the context adjoint gives g_scalars and the
+    V half of g_vmix; dWmix from (g_vmix, vectors) over the N * 3 rows; g_vectors = g_vmix Wmix."""
+
+    @staticmethod
+    def forward(ctx, scalars, vectors, blk, *params):
+        vec = vectors.detach().to(torch.float32).contiguous()
+        sc = scalars.detach().to(torch.float32)
+        if sc.stride(-1) != 1:
+            sc = sc.contiguous()
+        c = blk._packed_t()
+        s_out, v_out, saved = blk._run(c, sc, vec, save=True)
+        ctx.state = (blk, c, saved)
+        return s_out, v_out
+
+    @staticmethod
+    def backward(ctx, g_s_out, g_v_out):
+        from .gotennet import refuse_second_order
+        refuse_second_order("GatedEquivariantBlock.parameter_grads")
+        blk, c, (vec, vmix, cx, pre0, hid, x) = ctx.state
+        N = x.shape[0]
+        nv, ns, no, nh, nin = blk.n_vout, blk.n_sin, blk.n_sout, blk.n_hidden, blk.n_vin
+        pv, kc, po = c["pv"], c["kc"], c["po"]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+        g_s_out, g_v_out = g_s_out.to(torch.float32).contiguous(), g_v_out.to(torch.float32).contiguous()
+        need = ctx.needs_input_grad
+        g_x, g_vmix = new(N, po), new(N * 3, 2 * pv)
+        call("gn_geb_gate_backward", ptr(g_s_out), no, ptr(g_v_out), nv, ptr(x), po, no, nv, ptr(vmix), 2 * pv, pv, N,
+             blk.sact_kind, ptr(g_x), po, ptr(g_vmix), 2 * pv, engine._stream())
+        g_pre0, g_ctx, g_s = new(N, nh), new(N, kc), new(N, ns)
+        engine.gemm(g_x, po, c["w1t"], None, g_pre0, nh, N, nh, po, dgate=pre0, kind=blk.act_kind)
+        engine.gemm(g_pre0, nh, c["w0t"], None, g_ctx, kc, N, kc, nh, kind=blk.act_kind)
+        call("gn_geb_context_backward", ptr(g_ctx), kc, ns, ptr(vmix), 2 * pv, nv, pv, N, ptr(g_s), ns, ptr(g_vmix), 2 * pv,
+             engine._stream())
+        g_vec = None
+        if need[1]:
+            g_vec = new(N, 3, nin)
+            engine.gemm(g_vmix, 2 * pv, c["wmixt"], None, g_vec, nin, N * 3, nin, 2 * pv, kind=blk.act_kind)
+        probs, pg = [], [None] * 5
+        if need[3]:                                  # mix_vectors: the V rows, then the W rows
+            pg[0] = new(2 * nv, nin)
+            probs += [dict(dY=g_vmix, ldy=2 * pv, y_off=off, A=vec, lda=nin, dW=pg[0], w_row=row, rows=N * 3, nout=nv, K=nin)
+                      for off, row in ((0, 0), (pv, nv))]
+        if need[4] or need[5]:
+            pg[1], pg[2] = new(nh, ns + nv), new(nh)
+            probs.append(dict(dY=g_pre0, ldy=nh, A=cx, lda=kc, dW=pg[1], db=pg[2], rows=N, nout=nh, K=ns + nv))
+        if need[6] or need[7]:
+            pg[3], pg[4] = new(no + nv, nh), new(no + nv)
+            probs.append(dict(dY=g_x, ldy=po, A=hid, lda=nh, dW=pg[3], db=pg[4], rows=N, nout=no + nv, K=nh))
+        engine.weight_grad_group(probs)
+        pg = [g if need[3 + i] else None for i, g in enumerate(pg)]
+        return (g_s if need[0] else None, g_vec, None, *pg)
 
 
 def _field(inputs, name):
@@ -486,8 +578,9 @@ def _field(inputs, name):
 class Dipole(nn.Module):
     """Reference outputs.py:379-468: two GatedEquivariantBlocks on (h, X[:, :3]) -> atomic dipoles + charges,
     ``y = sum_atoms (mu_n + pos_n q_n)`` per molecule (its norm with ``predict_magnitude``).  ``mean`` / ``stddev`` are
-    plain attributes like in the reference (not in the state_dict).  Inference only (the QM9 task takes no derivative); its
-    parameters are not trained on the accelerated path (no parameter gradients)."""
+    plain, untrained attributes like in the reference (not in the state_dict).  ``parameter_grads = True`` (forwarded to
+    both blocks) trains it: a loss on ``y`` / ``y_vector`` reaches the blocks' parameters and (h, X), first order.  The QM9
+    task takes no derivative: ``pos`` is data, and a ``pos`` that requires grad is refused in that mode."""
 
     def __init__(self, n_in: int, n_hidden: Optional[int] = None, activation=F.silu, property: str = "dipole",
                  predict_magnitude: bool = False, output_v: bool = True, mean=None, stddev=None):
@@ -503,25 +596,74 @@ class Dipole(nn.Module):
         self.requires_dr = self.requires_stress = False
         self.aggregation_mode = "sum"
 
+    @property
+    def parameter_grads(self) -> bool:
+        return all(layer.parameter_grads for layer in self.equivariant_layers)
+
+    @parameter_grads.setter
+    def parameter_grads(self, on: bool):
+        for layer in self.equivariant_layers:
+            layer.parameter_grads = bool(on)
+
+    def _reduce(self, l1, l0, pos, mp, n_mol):
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=l0.device)
+        y = new(n_mol, 1) if self.predict_magnitude else new(n_mol, 3)
+        y_vec = new(n_mol, 3, 1) if self.output_v else None
+        call("gn_dipole_reduce", ptr(l1), 1, ptr(l0), 1, ptr(pos), ptr(mp), n_mol, *self._standardise(),
+             int(self.predict_magnitude), ptr(y), ptr(y_vec), engine._stream())
+        return y, y_vec
+
+    def _standardise(self):
+        """(scale, shift, standardise) of the charges, as the reduction kernels take them."""
+        std = self.stddev is not None
+        return (float(self.stddev) if std else 1.0, float(self.mean) if std else 0.0, int(std))
+
     def forward(self, inputs):
         pos, batch = _field(inputs, "pos"), _field(inputs, "batch")
         l0 = _field(inputs, "representation")
         l1 = _field(inputs, "vector_representation")[:, :3, :]
+        train = self.parameter_grads and torch.is_grad_enabled() and (
+            l0.requires_grad or l1.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if train and pos.requires_grad:              # before any launch
+            raise NotImplementedError("Dipole.parameter_grads: `pos` requires grad, but the trained read-out takes no "
+                                      "derivative with respect to positions (they are data here); detach them")
         for layer in self.equivariant_layers:
             l0, l1 = layer(l0, l1)
         n_mol = int(batch[-1].item()) + 1 if batch.numel() else 0
         mp = molecule_ptr(batch, n_mol)
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=l0.device)
-        y = new(n_mol, 1) if self.predict_magnitude else new(n_mol, 3)
-        y_vec = new(n_mol, 3, 1) if self.output_v else None
-        std = self.stddev is not None
-        call("gn_dipole_reduce", ptr(l1), 1, ptr(l0), 1, ptr(pos.detach().to(torch.float32).contiguous()), ptr(mp), n_mol,
-             float(self.stddev) if std else 1.0, float(self.mean) if std else 0.0, int(std), int(self.predict_magnitude),
-             ptr(y), ptr(y_vec), engine._stream())
+        pos = pos.detach().to(torch.float32).contiguous()
+        if train:
+            y, y_vec = _DipoleReduceFn.apply(l1, l0, self, pos, mp, n_mol)
+        else:
+            y, y_vec = self._reduce(l1, l0, pos, mp, n_mol)
         result = {self.property: y}
         if self.output_v:
             result[self.property + "_vector"] = y_vec
         return result
+
+
+class _DipoleReduceFn(torch.autograd.Function):
+    """(mu [N, 3, 1], q [N, 1]) -> (y, y_vector): the per-molecule reduction of ``Dipole`` with its adjoint
+    (gn_dipole_reduce_backward; the molecule's dipole is recomputed there in the forward's order)."""
+
+    @staticmethod
+    def forward(ctx, mu, q, head, pos, mp, n_mol):
+        mu, q = mu.detach().contiguous(), q.detach().contiguous()
+        y, y_vec = head._reduce(mu, q, pos, mp, n_mol)
+        ctx.state = (head, mu, q, pos, mp, n_mol)
+        return y, y_vec                              # (y_vec is None without ``output_v``)
+
+    @staticmethod
+    def backward(ctx, g_y, g_yvec):
+        from .gotennet import refuse_second_order
+        refuse_second_order("Dipole.parameter_grads")
+        head, mu, q, pos, mp, n_mol = ctx.state
+        g_mu, g_q = torch.empty_like(mu), torch.empty_like(q)
+        g_y = g_y.to(torch.float32).contiguous()
+        g_yvec = g_yvec.to(torch.float32).contiguous() if g_yvec is not None else None
+        call("gn_dipole_reduce_backward", ptr(g_y), ptr(g_yvec), ptr(mu), 1, ptr(q), 1, ptr(pos), ptr(mp), n_mol,
+             *head._standardise(), int(head.predict_magnitude), ptr(g_mu), 1, ptr(g_q), 1, engine._stream())
+        return g_mu, g_q, None, None, None, None
 
 
 #: standard atomic weights by atomic number (index 0: the dummy element, weight 1, as in ase.data.atomic_masses, which
@@ -535,8 +677,9 @@ _ATOMIC_MASS = [1.0, 1.008, 4.002602, 6.94, 9.0121831, 10.81, 12.011, 14.007, 15
 
 class ElectronicSpatialExtentV2(Atomwise):
     """Reference outputs.py:471-545: ``y = sum_atoms |pos_n - c|^2 x_n`` with ``x = out_net(h)`` (the raw MLP output:
-    the reference does not standardise here) and ``c`` the mass-weighted centroid of the molecule.  Inference only: its
-    parameters are not trained on the accelerated path (``parameter_grads`` is not honoured here)."""
+    the reference does not standardise here) and ``c`` the mass-weighted centroid of the molecule.  ``parameter_grads =
+    True`` trains the out_net (first order; ``pos`` is data and must not require grad then); ``contributions`` stay
+    detached."""
 
     def __init__(self, n_in: int, n_layers: int = 2, n_hidden: Optional[int] = None, activation=shifted_softplus,
                  property: str = "y", contributions: Optional[str] = None, mean=None, stddev=None, outnet=None,
@@ -560,12 +703,56 @@ class ElectronicSpatialExtentV2(Atomwise):
             if bool(((self.atomic_mass[zc] <= 0) | (z.long() != zc)).any()):
                 raise ValueError("ElectronicSpatialExtentV2: an atomic number has no entry in `atomic_mass` (built-in "
                                  "table: Z <= 36); pass atomic_mass= or load a reference checkpoint that carries it")
+        params = list(self.parameters()) if (self.parameter_grads and torch.is_grad_enabled()) else []
+        train = bool(params) and (h.requires_grad or any(p.requires_grad for p in params))
+        if train and pos.requires_grad:              # before any launch
+            raise NotImplementedError("ElectronicSpatialExtentV2.parameter_grads: `pos` requires grad, but the trained "
+                                      "read-out takes no derivative with respect to positions (they are data here); "
+                                      "detach them")
         mp, z32 = molecule_ptr(batch, n_mol), z.to(torch.int32)
-        _, x, _ = self.energy_raw(h.detach().contiguous(), z32, mp, n_mol, raw=True)
-        y = torch.empty((n_mol, 1), dtype=torch.float32, device=h.device)
-        call("gn_ese_reduce", ptr(x), ptr(pos.detach().to(torch.float32).contiguous()), ptr(z32), ptr(self.atomic_mass),
-             self.atomic_mass.numel(), ptr(mp), n_mol, ptr(y), engine._stream())
+        pos = pos.detach().to(torch.float32).contiguous()
+        if train:
+            y = _ESEParamFn.apply(h, self, z32, mp, n_mol, pos, *params)
+            x = self._last_y
+        else:
+            y, x, _ = self._raw_forward(h.detach().contiguous(), z32, mp, n_mol, pos)
         result = {self.property: y}
         if self.contributions:
             result[self.contributions] = x.reshape(-1, 1)
         return result
+
+    def _raw_forward(self, h, z32, mp, n_mol, pos, acts=None):
+        """-> (y [n_mol, 1], x [N] the raw out_net output, the out_net's tape)."""
+        _, x, tape = self.energy_raw(h, z32, mp, n_mol, raw=True, acts=acts)
+        y = torch.empty((n_mol, 1), dtype=torch.float32, device=h.device)
+        call("gn_ese_reduce", ptr(x), ptr(pos), ptr(z32), ptr(self.atomic_mass), self.atomic_mass.numel(), ptr(mp), n_mol,
+             ptr(y), engine._stream())
+        return y, x, tape
+
+
+class _ESEParamFn(torch.autograd.Function):
+    """h, *parameters -> ``ElectronicSpatialExtentV2``'s property with parameter gradients: gn_ese_reduce_backward spreads
+    the molecule's upstream gradient to u_n = g_y[b] |pos_n - c_b|^2, the per-atom gradient of the raw out_net output;
+    from there the out_net backward of ``_AtomwiseParamFn`` (scale 1, no atomref, no atom_scale)."""
+
+    @staticmethod
+    def forward(ctx, h, head, z32, mol_ptr, n_mol, pos, *params):
+        acts = []
+        hd = h.detach().contiguous()
+        layers, c = head._packed()
+        y, x, tape = head._raw_forward(hd, z32, mol_ptr, n_mol, pos, acts=acts)
+        head._last_y = x
+        ctx.state = (head, z32, mol_ptr, n_mol, pos, hd, tape, acts, layers, c, params)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        from .gotennet import refuse_second_order
+        refuse_second_order("ElectronicSpatialExtentV2.parameter_grads")
+        head, z32, mol_ptr, n_mol, pos, h, tape, acts, layers, c, params = ctx.state
+        u = torch.empty((h.shape[0], 1), dtype=torch.float32, device=h.device)
+        call("gn_ese_reduce_backward", ptr(g_y.to(torch.float32).contiguous()), ptr(pos), ptr(z32), ptr(head.atomic_mass),
+             head.atomic_mass.numel(), ptr(mol_ptr), n_mol, ptr(u), engine._stream())
+        g, grads = _out_net_backward(head, h, tape, acts, layers, c, u, [1.0])
+        pg = [grads.get(id(p)) if ctx.needs_input_grad[6 + i] else None for i, p in enumerate(params)]
+        return (g if ctx.needs_input_grad[0] else None, None, None, None, None, None, *pg)

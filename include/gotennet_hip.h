@@ -447,6 +447,29 @@ int gn_dipole_reduce(const float* mu, int ldm, const float* q, int ldq, const fl
  * mass [n_mass] indexed by atomic number. */
 int gn_ese_reduce(const float* x, const float* pos, const int* z, const float* mass, int n_mass, const int* mol_ptr,
                   int n_mol, float* y, void* stream);
+/* Backward of the four kernels above (first-order training of the read-outs).  Node-local or one
+ * workgroup per molecule with sums in a fixed order, no atomics: identical inputs give identical bits.
+ *   gn_geb_gate_backward: from g_s_out [N, ldgs] and g_v_out [N*3, ldgo] with the saved x and vmix:
+ *     g_x [N, ldgx] = [g_s_out sact'(s) | sum_m g_v_out[m] W[m] | zeros] and the W half of g_vmix [N*3, ldgv]:
+ *     columns [w_off, ldgv) = gate g_v_out, zeros past n_vout.
+ *   gn_geb_context_backward: g_s [N, lds] = g_ctx[:, :n_sin] and the V half of g_vmix: columns [0, w_off) =
+ *     g_ctx[n_sin + f] V[m, f] / ||V_f|| (exactly 0 where the norm is 0, torch.norm's subgradient), zeros past n_vout.
+ *   Together the two write every element of g_vmix. */
+int gn_geb_gate_backward(const float* g_s_out, int ldgs, const float* g_v_out, int ldgo, const float* x, int ldx,
+                         int n_sout, int n_vout, const float* vmix, int ldv, int w_off, int N, int sact,
+                         float* g_x, int ldgx, float* g_vmix, int ldgv, void* stream);
+int gn_geb_context_backward(const float* g_ctx, int ldc, int n_sin, const float* vmix, int ldv, int n_vout, int w_off,
+                            int N, float* g_s, int lds, float* g_vmix, int ldgv, void* stream);
+/* Dipole: d_b recomputed in the forward's order; g_d = g_y[b] d_b / |d_b| (magnitude; 0 where |d_b| = 0) or g_y[b, :];
+ * g_mu[n, m] = g_d[m] + g_yvec[b, m] (g_yvec may be NULL), g_q[n] = scale sum_m g_d[m] pos[n, m] (scale applies
+ * when standardise). */
+int gn_dipole_reduce_backward(const float* g_y, const float* g_yvec, const float* mu, int ldm, const float* q, int ldq,
+                              const float* pos, const int* mol_ptr, int n_mol, float scale, float shift,
+                              int standardise, int magnitude, float* g_mu, int ldgm, float* g_q, int ldgq,
+                              void* stream);
+/* ElectronicSpatialExtentV2: u[n] = g_y[b] |pos_n - c_b|^2 with the centroid computed as in gn_ese_reduce. */
+int gn_ese_reduce_backward(const float* g_y, const float* pos, const int* z, const float* mass, int n_mass,
+                           const int* mol_ptr, int n_mol, float* u, void* stream);
 
 /* ---- adjacent: radius graph (Distance.forward, layers.py:1588-1604) ----------------------- */
 /* torch_cluster.radius_graph(pos, r, batch, loop=True, max_num_neighbors) semantics: edges j->i with

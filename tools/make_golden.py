@@ -615,6 +615,55 @@ def qm9_heads_kat():
     print("kat_qm9_heads written:", sorted(k for k in out if "/" in k)[:6], "...", float(r1["property"][0]), float(r3["property"][0]))
 
 
+def qm9_head_grads_kat():
+    """Gradients of the two vector read-outs for the training path: the reference's own Dipole (both forms) and
+    ElectronicSpatialExtentV2 in fp64 on the inputs and weights of ``kat_qm9_heads``, a seeded cotangent per output, and
+    the reference autograd's gradients w.r.t. h, X and every parameter.  Arrays only: ``<head>/c_<output>`` (cotangents),
+    ``<head>/grad/h``, ``<head>/grad/X``, ``<head>/grad/<parameter>``."""
+    k = np.load(os.path.join(OUT, "kat_qm9_heads.npz"))
+    masses = np.asarray(k["masses"], dtype=np.float64)
+    sys.modules.setdefault("torch_scatter", types.ModuleType("torch_scatter"))
+    sys.modules["torch_scatter"].scatter = ref_shims._scatter
+    sys.modules.setdefault("ase", types.ModuleType("ase"))
+    sys.modules.setdefault("ase.data", types.ModuleType("ase.data"))
+    sys.modules["ase"].data = sys.modules["ase.data"]
+    sys.modules["ase.data"].atomic_masses = masses
+    from gotennet.models.components import outputs as ref_out
+    F_ = k["h"].shape[1]
+    heads = {
+        "dip_task": (ref_out.Dipole(n_in=F_, predict_magnitude=True, property="property", mean=torch.tensor(0.3),
+                                    stddev=torch.tensor(1.7)), ("property",)),
+        "dip_vec": (ref_out.Dipole(n_in=F_, n_hidden=32, activation=torch.nn.functional.silu, property="dipole"),
+                    ("dipole", "dipole_vector")),
+        "ese": (ref_out.ElectronicSpatialExtentV2(n_in=F_, property="property", contributions="contrib"), ("property",)),
+    }
+    sys.modules["ase.data"].atomic_masses = np.ones(120)      # what head_kat() expects
+
+    class _D(dict):
+        __getattr__ = dict.__getitem__
+    g = torch.Generator().manual_seed(61)
+    out = {}
+    for tag, (mod, outputs) in heads.items():
+        mod.load_state_dict({n[len(tag) + 1:]: torch.from_numpy(k[n]) for n in k.files if n.startswith(tag + "/")},
+                            strict=True)
+        mod = mod.double()
+        h = torch.from_numpy(k["h"]).double().requires_grad_(True)
+        X = torch.from_numpy(k["X"]).double().requires_grad_(True)
+        res = mod(_D(z=torch.from_numpy(k["z"]), batch=torch.from_numpy(k["batch"]), pos=torch.from_numpy(k["pos"]).double(),
+                     representation=h, vector_representation=X))
+        loss = 0.0
+        for name in outputs:
+            c = torch.randn(res[name].shape, generator=g, dtype=torch.float64)
+            out[f"{tag}/c_{name}"] = c.numpy()
+            loss = loss + (c * res[name]).sum()
+        names = [n for n, _ in mod.named_parameters()]
+        grads = torch.autograd.grad(loss, [h, X] + [p for _, p in mod.named_parameters()], allow_unused=True)
+        for n, gr, ref_t in zip(["h", "X"] + names, grads, [h, X] + [p for _, p in mod.named_parameters()]):
+            out[f"{tag}/grad/{n}"] = (torch.zeros_like(ref_t) if gr is None else gr).numpy()
+    np.savez_compressed(os.path.join(OUT, "kat_qm9_head_grads.npz"), **out)
+    print("kat_qm9_head_grads written:", len(out), "arrays,", os.path.getsize(os.path.join(OUT, "kat_qm9_head_grads.npz")), "bytes")
+
+
 #: tests/test_oracle_vs_reference_live.py: (lmax, sep_dir = sep_tensor, scale_edge); weights seeded_fill(100 + lmax)
 ORACLE_FP64_CASES = [(1, False, True), (2, True, False), (3, True, True), (4, True, False)]
 
@@ -666,6 +715,8 @@ if __name__ == "__main__":
         sh_kat_high()
     if not only or "kat_qm9_heads" in only:
         qm9_heads_kat()
+    if not only or "kat_qm9_head_grads" in only:      # (after kat_qm9_heads: it reads that fixture's inputs and weights)
+        qm9_head_grads_kat()
     if not only or "kat_head" in only:
         head_kat()
     if not only or "kat_oracle_fp64" in only:
