@@ -19,6 +19,7 @@ LMAX_SLICED = 0x100      # GN_LMAX_SLICED: OR-ed into the lmax argument of the m
 LMAX_MEAN, LMAX_MAX = 0x200, 0x400      # GN_LMAX_MEAN / GN_LMAX_MAX: the reference's aggr = "mean" / "max" (message entries)
 
 ACT_NONE = 11            # GN_ACT_NONE
+WGRAD_F32, WGRAD_F16X2 = 0, 2           # GN_WGRAD_*: the mode argument of gn_weight_grad_group_mode
 _P, _I, _F, _L, _D = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 
 # symbol -> argtypes (mirrors include/gotennet_hip.h one for one)
@@ -107,12 +108,15 @@ SIGNATURES = {
     "gn_radius_fill": [_P, _P, _I, _F, _I, _P, C.c_int64, _P, _P, _P, _P],
     "gn_weight_grad_workspace": [_P, _I],
     "gn_weight_grad_group": [_P, _I, _P, _L, _P],
+    "gn_weight_grad_workspace_mode": [_P, _I, _I],
+    "gn_weight_grad_group_mode": [_P, _I, _I, _P, _L, _P],
     "gn_embedding_grad": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "gn_layernorm_param_grad_workspace": [_I, _I],
     "gn_layernorm_param_grad": [_P, _P, _P, _F, _P, _I, _I, _I, _P, _P, _P, _P],
 }
 
-_LONG_RESULT = ("gn_split_bf16x3_size", "gn_split_f16x2_size", "gn_weight_grad_workspace", "gn_layernorm_param_grad_workspace")
+_LONG_RESULT = ("gn_split_bf16x3_size", "gn_split_f16x2_size", "gn_weight_grad_workspace", "gn_weight_grad_workspace_mode",
+                "gn_layernorm_param_grad_workspace")
 
 _lib = None
 

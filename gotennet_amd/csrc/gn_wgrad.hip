@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "gn_common.h"
+#include "gn_gemm.h"
 
 namespace gn {
 
@@ -125,9 +126,226 @@ static void wgrad_shape(const gn_wgrad_desc& d, int& S, int& rps, int& tn, int& 
     S = std::max(1, (d.rows + rps - 1) / rps);
 }
 
-static long wgrad_floats(const gn_wgrad_desc& d) {
+// ---------------------------------------------------------------------------------- weight gradients, f16x2 arithmetic
+// The same product as three fp16 MFMAs (v_mfma_f32_32x32x16_f16: hi*hi + hi*lo + lo*hi, fp32 accumulation) on operands
+// scaled by power-of-two block exponents and split into two fp16 planes (split4_f16, gn_gemm.h).
+//
+// Tile.  A workgroup of eight waves owns 128 outputs (nout) x 256 inputs (K): wave w accumulates the outputs
+// [32 (w & 3), +32) x the inputs [128 (w >> 2), +128) as four 32 x 32 tiles (64 accumulator registers).  For K <= 256
+// every dY element is fetched once per launch and every A element ceil(nout / 128) times.
+//
+// Exponents.  One per 32-column block and side (4 of dY, 8 of A): the running maximum, along the rows staged so far, of
+// the block's binary exponent, so that |x 2^-e| < 2^15.  They only grow; when one grows the accumulators that carry it
+// are rescaled by the exact power of two 2^-(growth) <= 1, and the epilogue multiplies by 2^(eY + eA).  A block whose
+// maximum is 0 gets the smallest exponent: 0 * 2^120 = 0, its products are exact zeros.  The maxima are combined over
+// the workgroup with LDS atomic max on the bit pattern of |x| (order-independent: identical inputs, identical bits).
+//
+// LDS.  Each stage of 32 rows is kept as row-major fp16 images (planes hi, lo) and the MFMA operands -- 8 consecutive
+// ROWS of one column per lane, for both sides -- are read with the transposed read of gfx950 (ds_read_b64_tr_b16): the
+// global reads stay row-contiguous and the stores are plain 8-byte writes of four neighbouring columns, where a
+// transposing store would need one 2-byte write per element.  Per 16 lanes a read takes 4 rows x 16 columns; lane
+// 4q + p supplies the address of row q, columns 4p .. 4p+3 (8 bytes, 8-byte aligned: the pitches are multiples of 4
+// elements) and lane i receives column i.  The images are padded to the full tile with zeros, so every lane of every
+// read is in bounds and no lane is masked (the read needs EXEC all ones; the only branches around it are wave-uniform).
+// Banks: a 32-lane half reads 4 rows x 64 contiguous bytes; the pitches (320 and 576 bytes) are 16 banks mod 64, so the
+// four rows fall in the four quarters of the 64 banks: conflict-free.
+constexpr int WH_TN = 128;                // output tile: nout
+constexpr int WH_TK = 256;                // output tile: K
+constexpr int WH_ROWS = 32;               // rows per LDS stage (two MFMA k-steps)
+constexpr int WH_PY = WH_TN + 32;         // fp16 per LDS row of a dY plane
+constexpr int WH_PA = WH_TK + 32;         // fp16 per LDS row of an A plane
+constexpr int WH_NBY = WH_TN / 32, WH_NBA = WH_TK / 32;
+constexpr int WH_EMIN = -120, WH_EMAX = 113;
+typedef short wh_i16x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ f16x4 lds_tr4(const _Float16* p) {
+    return __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+        (__attribute__((address_space(3))) wh_i16x4*)p));
+}
+__device__ __forceinline__ f16x8 lds_tr8(const _Float16* p, int pitch) {      // rows 0..3 and 4..7 of the lane's block
+    const f16x4 a = lds_tr4(p), b = lds_tr4(p + 4 * pitch);
+    return f16x8{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+}
+// maximum over each group of 8 consecutive lanes, valid in the group's last lane (row_shr 1/2/4, zero-filled)
+__device__ __forceinline__ unsigned group8_umax(unsigned v) {
+    auto mx = [](unsigned a, unsigned b) { return a > b ? a : b; };
+    v = mx(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));
+    v = mx(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));
+    v = mx(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));
+    return v;
+}
+__device__ __forceinline__ float absmax4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
+// block exponent of a maximum given as its bit pattern: |x| < 2^(e + 15)
+__device__ __forceinline__ int wh_exp(unsigned bits) {
+    const int e = (int)((bits >> 23) & 0xffu) - 126 - 15;
+    return e < WH_EMIN ? WH_EMIN : (e > WH_EMAX ? WH_EMAX : e);
+}
+// four consecutive columns from column c of a row with ncols valid columns; one 16-byte load only where `vec` says the
+// address is 16-byte aligned and all four are valid
+__device__ __forceinline__ float4 wh_load4(const float* q, int c, int ncols, bool vec) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c + 3 < ncols && vec) return *reinterpret_cast<const float4*>(q);
+    if (c < ncols) v.x = q[0];
+    if (c + 1 < ncols) v.y = q[1];
+    if (c + 2 < ncols) v.z = q[2];
+    if (c + 3 < ncols) v.w = q[3];
+    return v;
+}
+
+__global__ __launch_bounds__(512) void wgrad_f16_partial_kernel(const WgradArgs args) {
+    __shared__ __attribute__((aligned(16))) _Float16 sY[2][WH_ROWS][WH_PY];   // planes hi, lo
+    __shared__ __attribute__((aligned(16))) _Float16 sA[2][WH_ROWS][WH_PA];
+    __shared__ unsigned smax[WH_NBY + WH_NBA];       // running block maxima (bit patterns of |x|)
+    int pi = 0;
+    while (pi + 1 < args.n && (int)blockIdx.x >= args.p[pi + 1].blk0) ++pi;
+    const WgradProb& p = args.p[pi];
+    const int b = blockIdx.x - p.blk0;
+    const int tiles = p.tiles_n * p.tiles_k;
+    const int s = b / tiles, tile = b % tiles;
+    const int n0 = (tile / p.tiles_k) * WH_TN, k0 = (tile % p.tiles_k) * WH_TK;
+    const int r_begin = min(p.rows, s * p.rows_per_split), r_end = min(p.rows, r_begin + p.rows_per_split);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave & 3, wk = wave >> 2;
+    // this wave's tiles that hold any output (wave-uniform): the others are neither multiplied nor stored
+    const int krem = p.K - k0 - wk * 128;
+    const int nkt = (n0 + wn * 32 < p.nout && krem > 0) ? min(4, (krem + 31) / 32) : 0;
+    // staging: dY as 2 x (16 rows x 32 column quads), A as 4 x (8 rows x 64 column quads); four columns per thread
+    const int yq = tid & 31, yr = tid >> 5, aq = tid & 63, ar = tid >> 6;
+    const int yc = n0 + 4 * yq, ac = k0 + 4 * aq;
+    const bool yvec = (((size_t)p.dY | (size_t)(4 * p.ldy) | (size_t)(4 * p.y_off)) & 15) == 0;
+    const bool avec = (((size_t)p.A | (size_t)(4 * p.lda) | (size_t)(4 * p.a_off)) & 15) == 0;
+    const bool bias = p.db != nullptr && (tile % p.tiles_k) == 0;
+    f32x16 acc[4] = {};
+    int eYw = WH_EMIN, eAw[4] = {WH_EMIN, WH_EMIN, WH_EMIN, WH_EMIN};   // exponents the accumulators carry
+    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 ry[2], ra[4];
+    auto load = [&](int r0) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int r = r0 + yr + 16 * i;
+            ry[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < r_end && yc < p.nout) ry[i] = wh_load4(p.dY + wg_row(p, r) * p.ldy + p.y_off + yc, yc, p.nout, yvec);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = r0 + ar + 8 * i;
+            ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < r_end && ac < p.K) ra[i] = wh_load4(p.A + wg_row(p, r) * p.lda + p.a_off + ac, ac, p.K, avec);
+        }
+    };
+    if (tid < WH_NBY + WH_NBA) smax[tid] = 0u;
+    if (r_begin < r_end) load(r_begin);
+    __syncthreads();
+    // lane addresses of the transposed reads: row 8 (lane >> 5) + ((lane & 15) >> 2), column 16 ((lane >> 4) & 1) + 4 (lane & 3)
+    const int trow = 8 * (lane >> 5) + ((lane & 15) >> 2), tcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    for (int r0 = r_begin; r0 < r_end; r0 += WH_ROWS) {
+        {   // block maxima of this stage join the running ones (8 lanes share a 32-column block on either side)
+            const unsigned uy = group8_umax(__float_as_uint(fmaxf(absmax4(ry[0]), absmax4(ry[1]))));
+            const unsigned ua = group8_umax(__float_as_uint(fmaxf(fmaxf(absmax4(ra[0]), absmax4(ra[1])), fmaxf(absmax4(ra[2]), absmax4(ra[3])))));
+            if ((lane & 7) == 7) {
+                atomicMax(&smax[yq >> 3], uy);
+                atomicMax(&smax[WH_NBY + (aq >> 3)], ua);
+            }
+        }
+        __syncthreads();       // maxima complete; the previous stage's LDS reads are done
+        {
+            const int ey = wh_exp(smax[yq >> 3]), ea = wh_exp(smax[WH_NBY + (aq >> 3)]);
+            const float scy = __uint_as_float((unsigned)(127 - ey) << 23), sca = __uint_as_float((unsigned)(127 - ea) << 23);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                f16x4 h, l;
+                split4_f16(ry[i], scy, h, l);
+                *reinterpret_cast<f16x4*>(&sY[0][yr + 16 * i][4 * yq]) = h;
+                *reinterpret_cast<f16x4*>(&sY[1][yr + 16 * i][4 * yq]) = l;
+                if (bias) { bsum.x += ry[i].x; bsum.y += ry[i].y; bsum.z += ry[i].z; bsum.w += ry[i].w; }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                f16x4 h, l;
+                split4_f16(ra[i], sca, h, l);
+                *reinterpret_cast<f16x4*>(&sA[0][ar + 8 * i][4 * aq]) = h;
+                *reinterpret_cast<f16x4*>(&sA[1][ar + 8 * i][4 * aq]) = l;
+            }
+            // the exponents of this wave's tiles: rescale what has been accumulated under smaller ones
+            const int ny = __builtin_amdgcn_readfirstlane(wh_exp(smax[wn]));
+            const int dy = ny - eYw;
+            eYw = ny;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) {
+                const int na = __builtin_amdgcn_readfirstlane(wh_exp(smax[WH_NBY + 4 * wk + kt]));
+                const int d = dy + na - eAw[kt];
+                eAw[kt] = na;
+                if (d > 0 && kt < nkt) {
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) acc[kt][reg] = ldexpf(acc[kt][reg], -d);
+                }
+            }
+        }
+        __syncthreads();
+        if (r0 + WH_ROWS < r_end) load(r0 + WH_ROWS);    // next stage's global reads overlap this stage's MFMAs
+        if (nkt > 0) {
+#pragma unroll
+            for (int ks = 0; ks < WH_ROWS / 16; ++ks) {
+                const _Float16* yb = &sY[0][16 * ks + trow][32 * wn + tcol];
+                const f16x8 yh = lds_tr8(yb, WH_PY), yl = lds_tr8(yb + WH_ROWS * WH_PY, WH_PY);
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) {
+                    if (kt < nkt) {
+                        const _Float16* ab = &sA[0][16 * ks + trow][128 * wk + 32 * kt + tcol];
+                        const f16x8 ah = lds_tr8(ab, WH_PA), al = lds_tr8(ab + WH_ROWS * WH_PA, WH_PA);
+                        acc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(yh, al, acc[kt], 0, 0, 0);
+                        acc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(yl, ah, acc[kt], 0, 0, 0);
+                        acc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(yh, ah, acc[kt], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+    // C/D map of the 32x32 MFMA: column lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    float* part = p.part + (long)s * ((long)p.nout * p.K + p.nout);
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+        if (kt < nkt) {
+            const int kc = k0 + wk * 128 + kt * 32 + (lane & 31);
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int n = n0 + wn * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                if (n < p.nout && kc < p.K) part[(long)n * p.K + kc] = ldexpf(acc[kt][reg], eYw + eAw[kt]);
+            }
+        }
+    }
+    if (bias) {                // db: plain fp32 column sums; the 16 row groups of the staging are added in order
+        float* sB = reinterpret_cast<float*>(&sY[0][0][0]);      // [16][WH_TN] floats = 8 KiB of the dY images
+        __syncthreads();
+        *reinterpret_cast<float4*>(sB + yr * WH_TN + 4 * yq) = bsum;
+        __syncthreads();
+        if (tid < WH_TN && n0 + tid < p.nout) {
+            float v = 0.f;
+            for (int g = 0; g < 16; ++g) v += sB[g * WH_TN + tid];
+            part[(long)p.nout * p.K + n0 + tid] = v;
+        }
+    }
+}
+
+// the split of the rows for the f16x2 kernel: at least 512 rows per split, and about 512 workgroups for the problem
+static void wgrad_shape_f16(const gn_wgrad_desc& d, int& S, int& rps, int& tn, int& tk) {
+    tn = (d.nout + WH_TN - 1) / WH_TN;
+    tk = (d.K + WH_TK - 1) / WH_TK;
+    const int want = std::max(1, 512 / (tn * tk));
+    S = std::max(1, std::min(want, (d.rows + 511) / 512));
+    rps = ((d.rows + S - 1) / S + WH_ROWS - 1) / WH_ROWS * WH_ROWS;
+    if (rps == 0) rps = WH_ROWS;
+    S = std::max(1, (d.rows + rps - 1) / rps);
+}
+
+static void wgrad_shape_mode(const gn_wgrad_desc& d, int mode, int& S, int& rps, int& tn, int& tk) {
+    if (mode == GN_WGRAD_F16X2) wgrad_shape_f16(d, S, rps, tn, tk);
+    else wgrad_shape(d, S, rps, tn, tk);
+}
+
+static long wgrad_floats(const gn_wgrad_desc& d, int mode) {
     int S, rps, tn, tk;
-    wgrad_shape(d, S, rps, tn, tk);
+    wgrad_shape_mode(d, mode, S, rps, tn, tk);
     return (long)S * ((long)d.nout * d.K + d.nout);
 }
 
@@ -215,15 +433,17 @@ __global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __res
 
 }  // namespace gn
 
-extern "C" long gn_weight_grad_workspace(const gn_wgrad_desc* d, int n) {
+static bool wgrad_mode_ok(int mode) { return mode == GN_WGRAD_F32 || mode == GN_WGRAD_F16X2; }
+
+static long wgrad_workspace(const gn_wgrad_desc* d, int n, int mode) {
     long total = 0;
-    for (int i = 0; i < n; ++i) total += gn::wgrad_floats(d[i]);
+    for (int i = 0; i < n; ++i) total += gn::wgrad_floats(d[i], mode);
     return total;
 }
 
-extern "C" int gn_weight_grad_group(const gn_wgrad_desc* d, int n, float* work, long work_floats, void* stream) {
+static int wgrad_group(const gn_wgrad_desc* d, int n, int mode, float* work, long work_floats, void* stream) {
     if (n < 0 || (n > 0 && (d == nullptr || work == nullptr))) return GN_ERR_BAD_ARG;
-    if (gn_weight_grad_workspace(d, n) > work_floats) return GN_ERR_BAD_ARG;
+    if (wgrad_workspace(d, n, mode) > work_floats) return GN_ERR_BAD_ARG;
     for (int i = 0; i < n; ++i) {
         const gn_wgrad_desc& q = d[i];
         if (q.rows < 0 || q.nout < 1 || q.K < 1 || q.row_cnt < 1 || q.dW == nullptr || q.ldw < q.K ||
@@ -239,7 +459,7 @@ extern "C" int gn_weight_grad_group(const gn_wgrad_desc* d, int n, float* work, 
         for (int j = 0; j < ga.n; ++j) {
             const gn_wgrad_desc& q = d[i0 + j];
             gn::WgradProb& p = ga.p[j];
-            gn::wgrad_shape(q, p.S, p.rows_per_split, p.tiles_n, p.tiles_k);
+            gn::wgrad_shape_mode(q, mode, p.S, p.rows_per_split, p.tiles_n, p.tiles_k);
             p.dY = q.dY; p.A = q.A; p.dW = q.dW; p.db = q.db; p.part = wp;
             p.ldy = q.ldy; p.y_off = q.y_off; p.lda = q.lda; p.a_off = q.a_off; p.ldw = q.ldw;
             p.rows = q.rows; p.nout = q.nout; p.K = q.K;
@@ -248,15 +468,33 @@ extern "C" int gn_weight_grad_group(const gn_wgrad_desc* d, int n, float* work, 
             p.red0 = red;
             blocks += p.S * p.tiles_n * p.tiles_k;
             red += (long)q.nout * q.K + q.nout;
-            wp += gn::wgrad_floats(q);
+            wp += gn::wgrad_floats(q, mode);
         }
-        hipLaunchKernelGGL(gn::wgrad_partial_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ga);
+        if (mode == GN_WGRAD_F16X2)
+            hipLaunchKernelGGL(gn::wgrad_f16_partial_kernel, dim3(blocks), dim3(512), 0, (hipStream_t)stream, ga);
+        else
+            hipLaunchKernelGGL(gn::wgrad_partial_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ga);
         GN_LAUNCH_CHECK();
         hipLaunchKernelGGL(gn::wgrad_reduce_kernel, dim3((unsigned)((red + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            ga, red);
         GN_LAUNCH_CHECK();
     }
     return GN_OK;
+}
+
+extern "C" long gn_weight_grad_workspace(const gn_wgrad_desc* d, int n) { return wgrad_workspace(d, n, GN_WGRAD_F32); }
+
+extern "C" int gn_weight_grad_group(const gn_wgrad_desc* d, int n, float* work, long work_floats, void* stream) {
+    return wgrad_group(d, n, GN_WGRAD_F32, work, work_floats, stream);
+}
+
+extern "C" long gn_weight_grad_workspace_mode(const gn_wgrad_desc* d, int n, int mode) {
+    return wgrad_mode_ok(mode) ? wgrad_workspace(d, n, mode) : -1;
+}
+
+extern "C" int gn_weight_grad_group_mode(const gn_wgrad_desc* d, int n, int mode, float* work, long work_floats, void* stream) {
+    if (!wgrad_mode_ok(mode)) return GN_ERR_BAD_ARG;
+    return wgrad_group(d, n, mode, work, work_floats, stream);
 }
 
 extern "C" int gn_embedding_grad(const float* g_ctx, const float* feat, int ldf, const float* cut, const int* dst,

@@ -121,6 +121,7 @@ class Config:
     evec: int = 0             # evec_dim: width of EQ / EK / w (0 = F; != F needs W_edp to map back to F)
     emlp: int = 0             # emlp_dim: hidden width of the 2-layer gamma_t (0 = F)
     gemm_mode: str = ""       # projection arithmetic of THIS model ("f16x2" | "split" | "f32"; "" = engine.GEMM_MODE, the default)
+    wgrad_mode: str = ""      # weight-gradient arithmetic of THIS model ("f32" | "f16x2"; "" = engine.WGRAD_MODE, the default)
     sliced: bool = False      # run lmax <= 4 on the degree-sliced kernel family too (GN_LMAX_SLICED in the lmax argument)
     aggr: int = 0             # the reference's `aggr` (gotennet.py:84,638): 0 "add", 1 "mean", 2 "max"
     Fc: int = 0               # width of the NodeInit LayerNorm intermediate when the model is embedded in a power-of-two F (embed.py; 0 = F)
@@ -220,6 +221,24 @@ def resolve_mode(mode: Optional[str]) -> str:
     mode = mode or GEMM_MODE
     if mode not in MODES:
         raise ValueError(f"projection arithmetic {mode!r}: one of {MODES}")
+    return mode
+
+
+#: DEFAULT arithmetic of the weight gradients dW = dY^T A (``weight_grad_group``) of a module that does not choose one
+#: (``wgrad_mode = None`` on GotenNet and the output heads; env GN_WGRAD_MODE sets the default at import).
+#:   "f32" (default) -- exact fp32 MFMA (v_mfma_f32_32x32x2_f32), gn_weight_grad_group.
+#:   "f16x2" -- both operands as two fp16 planes scaled by block exponents (one per 32-column block and side, running
+#:       maximum along the rows), three fp16 MFMAs per product, fp32 accumulate (gn_weight_grad_group_mode, DESIGN
+#:       section 7).  Opt-in; identical inputs give identical bits.
+WGRAD_MODE = os.environ.get("GN_WGRAD_MODE", "f32")
+WGRAD_MODES = ("f32", "f16x2")
+_WGRAD_CODE = {"f32": _lib.WGRAD_F32, "f16x2": _lib.WGRAD_F16X2}
+
+
+def resolve_wgrad_mode(mode: Optional[str]) -> str:
+    mode = mode or WGRAD_MODE
+    if mode not in WGRAD_MODES:
+        raise ValueError(f"weight-gradient arithmetic {mode!r}: one of {WGRAD_MODES}")
     return mode
 
 
@@ -842,10 +861,12 @@ def _edge_update_composed_backward(cfg: Config, lw: LayerWeights, lt, gt, gt_a, 
     return gq
 
 
-def weight_grad_group(problems):
+def weight_grad_group(problems, mode: Optional[str] = None):
     """Several independent weight gradients dW = dY^T A (+ db = sum_r dY) as one launch (gn_weight_grad_group).  A
     problem is a dict: dY, ldy, A, lda, dW (its rows [w_row, w_row + nout) are written), rows, nout, K; optional y_off,
-    a_off (column offsets), db (with b_row), rowmap (cnt, gstride, goff)."""
+    a_off (column offsets), db (with b_row), rowmap (cnt, gstride, goff).  ``mode``: the arithmetic (``WGRAD_MODES``;
+    None = ``WGRAD_MODE``); anything but "f32" goes through gn_weight_grad_group_mode."""
+    mode = resolve_wgrad_mode(mode)
     problems = [q for q in problems if q is not None]
     if not problems:
         return
@@ -860,10 +881,14 @@ def weight_grad_group(problems):
         d.db = (db.data_ptr() + 4 * g("b_row", 0)) if db is not None else None
         d.rows, d.nout, d.K = q["rows"], q["nout"], q["K"]
         d.row_cnt, d.row_gstride, d.row_goff = g("rowmap", (1, 1, 0))
-    lib = _lib.load()
-    work = torch.empty(max(1, lib.gn_weight_grad_workspace(arr, len(problems))), dtype=torch.float32,
-                       device=problems[0]["dW"].device)
-    call("gn_weight_grad_group", arr, len(problems), ptr(work), work.numel(), _stream())
+    lib, dev = _lib.load(), problems[0]["dW"].device
+    if mode == "f32":
+        work = torch.empty(max(1, lib.gn_weight_grad_workspace(arr, len(problems))), dtype=torch.float32, device=dev)
+        call("gn_weight_grad_group", arr, len(problems), ptr(work), work.numel(), _stream())
+        return
+    code = _WGRAD_CODE[mode]
+    work = torch.empty(max(1, lib.gn_weight_grad_workspace_mode(arr, len(problems), code)), dtype=torch.float32, device=dev)
+    call("gn_weight_grad_group_mode", arr, len(problems), code, ptr(work), work.numel(), _stream())
 
 
 def layernorm_param_grad(x, gamma, beta, g_out, act: int, dgamma, dbeta):
@@ -1028,7 +1053,7 @@ def _layer_weight_grads_eqff_htr(cfg: Config, gw: LayerWeights, lt: LayerTape, w
                   dict(dY=wb.gEQ, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvq, rows=N * D, nout=Fe, K=F_)]
         probs += [dict(dY=wb.gEK, ldy=Fe, A=lt.X_msg, lda=F_, dW=gw.Wvk[k], rows=rows, nout=Fe, K=F_, rowmap=rowmap)
                   for k, rows, rowmap in cfg.degree_blocks(N)]
-    weight_grad_group(probs)
+    weight_grad_group(probs, cfg.wgrad_mode)
 
 
 def _gata_backward(p: _Call, lw: LayerWeights, lt: LayerTape, wb: _BackwardWork, li: int, gt_in, gw):
@@ -1086,7 +1111,8 @@ def _layer_weight_grads_gata(p: _Call, gw: LayerWeights, lt: LayerTape, wb: _Bac
         dict(dY=wb.g_eproj, ldy=lde, A=lt.t_in, lda=F_, dW=gw.We, db=gw.be, rows=E, nout=ne, K=F_),
         dict(dY=wb.g_nproj, ldy=4 * F_, A=lt.h_in, lda=F_, dW=gw.Wn1, db=gw.bn1, rows=N, nout=4 * F_, K=F_),
         dict(dY=wb.g_x, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=2 * F_, dW=gw.Ws2, db=gw.bs2, rows=N, nout=nv, K=F_),
-        dict(dY=wb.g_v, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=3 * F_, dW=gw.Wv2, db=gw.bv2, rows=N, nout=nv, K=F_)])
+        dict(dY=wb.g_v, ldy=M * F_, A=lt.nact, lda=4 * F_, a_off=3 * F_, dW=gw.Wv2, db=gw.bv2, rows=N, nout=nv, K=F_)],
+        p.cfg.wgrad_mode)
     if lt.first:                                   # a zero-X_in layer: the tensor-gate rows get exactly zero
         for t_, n in ((gw.We, ne), (gw.be, ne), (gw.Ws2, nv), (gw.bs2, nv), (gw.Wv2, nv), (gw.bv2, nv)):
             t_[n:].zero_()
@@ -1117,7 +1143,8 @@ def _init_weight_grads(cfg, pw: PackedWeights, gw: PackedWeights, z32, g: Graph,
     layernorm_param_grad(tape.y_pre, pw.ln_w, pw.ln_b, gy, cfg.act, gw.ln_w, gw.ln_b)
     weight_grad_group([dict(dY=wb.gh, ldy=F_, A=tape.y, lda=Fc, dW=gw.Wb, db=gw.bb, rows=N, nout=F_, K=Fc),
                        dict(dY=gy1, ldy=Fc, A=tape.ctx0, lda=2 * F_, dW=gw.Wa, db=gw.ba, rows=N, nout=Fc, K=2 * F_),
-                       dict(dY=g_feat, ldy=2 * F_, A=g.phi, lda=R, dW=gw.Winit, db=gw.binit, rows=E, nout=2 * F_, K=R)])
+                       dict(dY=g_feat, ldy=2 * F_, A=g.phi, lda=R, dW=gw.Winit, db=gw.binit, rows=E, nout=2 * F_, K=R)],
+                      cfg.wgrad_mode)
     # species order of the atoms (integer plumbing): a stable argsort of z and the first sorted position of each species
     n_sp = pw.A_na.shape[0]
     zs, order = torch.sort(z32.long(), stable=True)

@@ -568,6 +568,9 @@ class GotenNet(nn.Module):
         #: projection arithmetic of THIS model: None = ``engine.GEMM_MODE`` (the process default), or "f16x2" / "split" /
         #: "f32" (engine.py).  Carried in ``config()``: two models with different arithmetics may run from two threads.
         self.gemm_mode: Optional[str] = None
+        #: arithmetic of the weight gradients of THIS model in a ``parameter_grads`` backward: None = ``engine.WGRAD_MODE``
+        #: (the process default, "f32"), or "f32" / "f16x2" (engine.py).  Carried in ``config()`` like ``gemm_mode``.
+        self.wgrad_mode: Optional[str] = None
         #: True: lmax <= 4 runs on the degree-sliced kernel family as well (GN_LMAX_SLICED; tests hold the two families
         #: against each other)
         self.sliced_kernels = False
@@ -662,7 +665,9 @@ class GotenNet(nn.Module):
                              t_last_act=0 if g0.update_info["mlp"] else 3,
                              lin_w=g0.update_info["lin_w"], lin_ln=g0.update_info["lin_ln"],
                              evec=g0.edge_vec_dim, emlp=g0.edge_mlp_dim, act=self.act_kind,
-                             gemm_mode=engine.resolve_mode(self.gemm_mode), sliced=bool(self.sliced_kernels),
+                             gemm_mode=engine.resolve_mode(self.gemm_mode),
+                             wgrad_mode=engine.resolve_wgrad_mode(getattr(self, "wgrad_mode", None)),
+                             sliced=bool(self.sliced_kernels),
                              fuse_eqff=self.fuse_eqff, aggr=g0.aggr_kind)
 
     def _param_slots(self):

@@ -99,6 +99,8 @@ class Atomwise(nn.Module):
         #: True: with grad mode on and a parameter requiring grad, ``forward`` also returns d loss / d parameter for the
         #: out_net layers (first order; a backward with create_graph=True is refused)
         self.parameter_grads = False
+        #: arithmetic of those weight gradients: None = ``engine.WGRAD_MODE`` (the default, "f32"), or "f32" / "f16x2"
+        self.wgrad_mode: Optional[str] = None
 
     # ---- raw (non-autograd) pieces used by the fused pipeline -----------------------
     def invalidate_packed(self):
@@ -399,7 +401,7 @@ def _out_net_backward(head, h, tape, acts, layers, c, u, scales, weights: bool =
         g = gi
     if not weights:
         return g, {}
-    engine.weight_grad_group(probs)
+    engine.weight_grad_group(probs, getattr(head, "wgrad_mode", None))
     return g, grads
 
 
@@ -430,6 +432,8 @@ class GatedEquivariantBlock(nn.Module):
         #: True: with grad mode on and an input or parameter requiring grad, ``forward`` is differentiable (first order):
         #: dL/dscalars, dL/dvectors and d loss / d parameter; a backward with create_graph=True is refused
         self.parameter_grads = False
+        #: arithmetic of the weight gradients: None = ``engine.WGRAD_MODE`` (the default, "f32"), or "f32" / "f16x2"
+        self.wgrad_mode: Optional[str] = None
 
     def invalidate_packed(self):
         self._cache = None
@@ -566,7 +570,7 @@ class _GatedBlockParamFn(torch.autograd.Function):
         if need[6] or need[7]:
             pg[3], pg[4] = new(no + nv, nh), new(no + nv)
             probs.append(dict(dY=g_x, ldy=po, A=hid, lda=nh, dW=pg[3], db=pg[4], rows=N, nout=no + nv, K=nh))
-        engine.weight_grad_group(probs)
+        engine.weight_grad_group(probs, getattr(blk, "wgrad_mode", None))
         pg = [g if need[3 + i] else None for i, g in enumerate(pg)]
         return (g_s if need[0] else None, g_vec, None, *pg)
 
@@ -604,6 +608,16 @@ class Dipole(nn.Module):
     def parameter_grads(self, on: bool):
         for layer in self.equivariant_layers:
             layer.parameter_grads = bool(on)
+
+    @property
+    def wgrad_mode(self) -> Optional[str]:
+        """Weight-gradient arithmetic of both blocks (None = ``engine.WGRAD_MODE``); forwarded like ``parameter_grads``."""
+        return self.equivariant_layers[0].wgrad_mode
+
+    @wgrad_mode.setter
+    def wgrad_mode(self, mode: Optional[str]):
+        for layer in self.equivariant_layers:
+            layer.wgrad_mode = mode
 
     def _reduce(self, l1, l0, pos, mp, n_mol):
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=l0.device)

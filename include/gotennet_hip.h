@@ -509,6 +509,18 @@ typedef struct gn_wgrad_desc {
 } gn_wgrad_desc;
 long gn_weight_grad_workspace(const gn_wgrad_desc* problems, int n);
 int gn_weight_grad_group(const gn_wgrad_desc* problems, int n, float* work, long work_floats, void* stream);
+/* The same problems in a chosen arithmetic.  mode GN_WGRAD_F32 (0) forwards to the two entries above: same launches,
+ * same bits.  mode GN_WGRAD_F16X2 (2, numbered like the `split` argument of the projection launcher): each operand as
+ * two fp16 planes scaled by power-of-two exponents -- one per 32-column block and side, the running maximum along the
+ * rows, accumulators rescaled when it grows -- and three v_mfma_f32_32x32x16_f16 per product (hi*hi + hi*lo + lo*hi,
+ * fp32 accumulation) on a 128 (nout) x 256 (K) workgroup tile; an all-zero block gives exact zeros; db stays a plain
+ * fp32 column sum.  Same descriptor contract, same partial-sum workspace layout and in-order reduction (no atomics in
+ * global memory: identical inputs give identical bits); the row split, and so the workspace size, depends on the mode.
+ * Any other mode: gn_weight_grad_group_mode returns GN_ERR_BAD_ARG, gn_weight_grad_workspace_mode -1. */
+#define GN_WGRAD_F32 0
+#define GN_WGRAD_F16X2 2
+long gn_weight_grad_workspace_mode(const gn_wgrad_desc* problems, int n, int mode);
+int gn_weight_grad_group_mode(const gn_wgrad_desc* problems, int n, int mode, float* work, long work_floats, void* stream);
 /* Embedding gradients of NodeInit (layers.py:1658-1675; gotennet.py:969-975):
  * dA_na[s] = sum_{i: z_i = s} g_ctx[i, 0:F] (row 0, the padding_idx, is zero);
  * dA_nbr[s] = sum over the non-self-loop edges e = (j -> i) with z_j = s of g_ctx[i, F:2F] feat[e, 0:F] cut[e]: first per
