@@ -106,6 +106,11 @@ SIGNATURES = {
     "gn_ese_reduce_backward": [_P, _P, _P, _P, _I, _P, _I, _P, _P],
     "gn_radius_count": [_P, _P, _I, _F, _I, _P, _P],
     "gn_radius_fill": [_P, _P, _I, _F, _I, _P, C.c_int64, _P, _P, _P, _P],
+    "gn_cell_prepare": [_P, _I, _P, _P, _P],
+    "gn_radius_count_pbc": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P],
+    "gn_radius_fill_pbc": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, C.c_int64, _P, _P, _P, _P, _P],
+    "gn_edge_vectors_pbc": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
+    "gn_virial": [_P, _P, _P, _P, _P, _I, _P, _P, _P],
     "gn_weight_grad_workspace": [_P, _I],
     "gn_weight_grad_group": [_P, _I, _P, _L, _P],
     "gn_weight_grad_workspace_mode": [_P, _I, _I],

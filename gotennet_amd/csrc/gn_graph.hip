@@ -166,6 +166,166 @@ __global__ void molecule_ptr_kernel(const int64_t* __restrict__ batch, int N, in
     for (int64_t m = lo; m <= hi && m <= n_mol; ++m) mol_ptr[m] = n;
 }
 
+
+// ================================================================================ periodic boundary conditions
+// Conventions (include/gotennet_hip.h): cell fp32 [n_mol, 3, 3], ROWS are the lattice vectors a, b, c, one cell per entry of
+// `batch` (a "molecule" is a periodic box); edge_shift int32 [E, 3]; edge_vec[e] = pos[j] - pos[i] + edge_shift[e] @ cell.
+// Minimum image only: the host refuses cells whose perpendicular widths are below 2 * cutoff, so each pair has at most one
+// image inside the cutoff and that image has all fractional coordinates in (-1/2, 1/2): rounding the fractional difference
+// finds it, for skewed cells too.
+struct Image {
+    float vx, vy, vz, d2;
+    int sx, sy, sz;
+};
+// v = d + s @ cell and |v|^2: the ONLY place a shifted edge vector is computed (the fixed-list kernel calls it with the
+// stored shift, count and fill through image_of below).  The shift always passes through int, so a recomputed and a
+// stored one give the same bits; fmaf in the order a, b, c; d^2 accumulated x, y, z as in within().
+__device__ __forceinline__ Image shifted(float dx, float dy, float dz, int sx, int sy, int sz, const float* __restrict__ c) {
+    const float fx = (float)sx, fy = (float)sy, fz = (float)sz;
+    Image im;
+    im.sx = sx; im.sy = sy; im.sz = sz;
+    im.vx = fmaf(fz, c[6], fmaf(fy, c[3], fmaf(fx, c[0], dx)));
+    im.vy = fmaf(fz, c[7], fmaf(fy, c[4], fmaf(fx, c[1], dy)));
+    im.vz = fmaf(fz, c[8], fmaf(fy, c[5], fmaf(fx, c[2], dz)));
+    float d = im.vx * im.vx;
+    d += im.vy * im.vy;
+    d += im.vz * im.vz;
+    im.d2 = d;
+    return im;
+}
+// the minimum image of the pair (j -> i): d = pos[j] - pos[i], n_k = rint(d . column k of inv_cell), shift = -n
+__device__ __forceinline__ Image image_of(const float* __restrict__ pos, int i, int j, const float* __restrict__ c,
+                                          const float* __restrict__ ic) {
+    const float dx = pos[3 * j] - pos[3 * i], dy = pos[3 * j + 1] - pos[3 * i + 1], dz = pos[3 * j + 2] - pos[3 * i + 2];
+    const int nx = (int)rintf(fmaf(dz, ic[6], fmaf(dy, ic[3], dx * ic[0])));
+    const int ny = (int)rintf(fmaf(dz, ic[7], fmaf(dy, ic[4], dx * ic[1])));
+    const int nz = (int)rintf(fmaf(dz, ic[8], fmaf(dy, ic[5], dx * ic[2])));
+    return shifted(dx, dy, dz, -nx, -ny, -nz, c);
+}
+
+// one thread per box: inverse and |det| of its cell (on the device, so a recorded step follows a changing cell)
+__global__ void cell_prepare_kernel(const float* __restrict__ cell, int n_mol, float* __restrict__ inv_cell,
+                                    float* __restrict__ volume) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_mol) return;
+    const float* c = cell + 9 * m;
+    const float a0 = c[0], a1 = c[1], a2 = c[2], b0 = c[3], b1 = c[4], b2 = c[5], c0 = c[6], c1 = c[7], c2 = c[8];
+    const float k00 = b1 * c2 - b2 * c1, k01 = b2 * c0 - b0 * c2, k02 = b0 * c1 - b1 * c0;      // b x c
+    const float det = a0 * k00 + a1 * k01 + a2 * k02;
+    const float r = 1.0f / det;
+    float* o = inv_cell + 9 * m;                       // inverse = adjugate / det (row-major)
+    o[0] = k00 * r; o[1] = (a2 * c1 - a1 * c2) * r; o[2] = (a1 * b2 - a2 * b1) * r;
+    o[3] = k01 * r; o[4] = (a0 * c2 - a2 * c0) * r; o[5] = (a2 * b0 - a0 * b2) * r;
+    o[6] = k02 * r; o[7] = (a1 * c0 - a0 * c1) * r; o[8] = (a0 * b1 - a1 * b0) * r;
+    volume[m] = fabsf(det);
+}
+
+// The box of target i: its atom range from mol_ptr (never a backward scan of `batch`: a box holds hundreds to thousands of
+// atoms).  A batch entry outside [0, n_mol) is clamped and gn_molecule_ptr keeps every offset in [0, N]: a bad batch vector
+// gives a wrong list, never an out-of-bounds access.
+__device__ __forceinline__ int box_of(const int64_t* __restrict__ batch, int i, int n_mol) {
+    const int64_t b = batch[i];
+    return b < 0 ? 0 : (b >= n_mol ? n_mol - 1 : (int)b);
+}
+
+// One wave64 per target atom.  The lanes stride over the box's atoms, 64 per trip; a ballot plus the popcount of the lower
+// lanes gives each hit its slot in source order, and the wave-uniform running count `c` carries the cap across trips: the
+// first max_nbr sources in source order, deterministic, no atomics.  FILL = false counts (deg), FILL = true writes the list
+// -- ONE body, so the two cannot disagree about which pair is a hit (a count and a fill that disagree write out of bounds;
+// the fill checks its slot against E all the same).
+template <bool FILL>
+__global__ __launch_bounds__(256) void radius_pbc_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch,
+                                                         const int* __restrict__ mol_ptr, const float* __restrict__ cell,
+                                                         const float* __restrict__ inv_cell, int N, int n_mol, float r2,
+                                                         int max_nbr, int* __restrict__ deg,
+                                                         const int64_t* __restrict__ rowptr, int64_t E,
+                                                         int64_t* __restrict__ edge_index, int* __restrict__ edge_shift,
+                                                         float* __restrict__ edge_vec, float* __restrict__ edge_diff) {
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= N) return;                                // (wave-uniform)
+    const int m = box_of(batch, i, n_mol);
+    const int j0 = mol_ptr[m], j1 = mol_ptr[m + 1];
+    const float* c = cell + 9 * m;
+    const float* ic = inv_cell + 9 * m;
+    const int64_t e0 = FILL ? rowptr[i] : 0;
+    int cnt = 0;
+    for (int base = j0; base < j1 && cnt < max_nbr; base += 64) {
+        const int j = base + lane;
+        Image im;
+        bool hit = false;
+        if (j < j1) {
+            im = image_of(pos, i, j, c, ic);
+            hit = im.d2 < r2;
+        }
+        const unsigned long long mask = __ballot(hit);
+        if (FILL && hit) {
+            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+            const int64_t e = e0 + slot;
+            if (slot < max_nbr && e < E) {
+                edge_index[e] = j;                     // row 0: source
+                edge_index[E + e] = i;                 // row 1: target
+                edge_shift[3 * e] = im.sx; edge_shift[3 * e + 1] = im.sy; edge_shift[3 * e + 2] = im.sz;
+                edge_vec[3 * e] = im.vx; edge_vec[3 * e + 1] = im.vy; edge_vec[3 * e + 2] = im.vz;
+                edge_diff[e] = (j == i) ? 0.0f : sqrtf(im.d2);
+            }
+        }
+        cnt += __popcll(mask);
+    }
+    if (!FILL && lane == 0) deg[i] = cnt < max_nbr ? cnt : max_nbr;
+}
+
+// edge vectors of a FIXED periodic edge list for new positions / a new cell: the stored shift, no image search
+__global__ void edge_vectors_pbc_kernel(const float* __restrict__ pos, const int* __restrict__ src, const int* __restrict__ dst,
+                                        const int* __restrict__ shift, const float* __restrict__ cell,
+                                        const int64_t* __restrict__ batch, int E, int n_mol, float* __restrict__ edge_vec,
+                                        float* __restrict__ edge_diff) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const int j = src[e], i = dst[e];
+    const float dx = pos[3 * j] - pos[3 * i], dy = pos[3 * j + 1] - pos[3 * i + 1], dz = pos[3 * j + 2] - pos[3 * i + 2];
+    const Image im = shifted(dx, dy, dz, shift[3 * e], shift[3 * e + 1], shift[3 * e + 2], cell + 9 * box_of(batch, i, n_mol));
+    edge_vec[3 * e] = im.vx; edge_vec[3 * e + 1] = im.vy; edge_vec[3 * e + 2] = im.vz;
+    edge_diff[e] = (j == i) ? 0.0f : sqrtf(im.d2);
+}
+
+// out[m] = (1 / volume[m]) sum_{e in box m} r_e (x) dE/dr_e,  dE/dr_e = g_vec + g_diff r / |r| (gn_pos_scatter's expression).
+// One workgroup per box over its contiguous edge range; nine sums, wave_sum, then the waves in order through LDS: no
+// atomics, identical inputs give identical bits.  An empty box gives zeros.
+__global__ __launch_bounds__(256) void virial_kernel(const float* __restrict__ g_vec, const float* __restrict__ g_diff,
+                                                     const float* __restrict__ vec, const int* __restrict__ rowptr,
+                                                     const int* __restrict__ mol_ptr, const float* __restrict__ volume,
+                                                     float* __restrict__ out) {
+    __shared__ float part[4][9];
+    const int m = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int e0 = rowptr[mol_ptr[m]], e1 = rowptr[mol_ptr[m + 1]];
+    float s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = 0.f;
+    for (int e = e0 + (int)threadIdx.x; e < e1; e += 256) {
+        const float x = vec[3 * e], y = vec[3 * e + 1], z = vec[3 * e + 2];
+        const float gd = g_diff[e];
+        float rx = g_vec[3 * e], ry = g_vec[3 * e + 1], rz = g_vec[3 * e + 2];
+        if (gd != 0.f) {
+            const float q = gd / sqrtf(x * x + y * y + z * z);
+            rx += q * x; ry += q * y; rz += q * z;
+        }
+        s[0] += x * rx; s[1] += x * ry; s[2] += x * rz;
+        s[3] += y * rx; s[4] += y * ry; s[5] += y * rz;
+        s[6] += z * rx; s[7] += z * ry; s[8] += z * rz;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const float t = wave_sum(s[k]);
+        if (lane == 0) part[wave][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {
+        const int k = threadIdx.x;
+        const float t = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
+        out[9 * m + k] = t / volume[m];
+    }
+}
+
 }  // namespace gn
 
 extern "C" int gn_build_csc(const int* src, const int* dst, int E, int N, int* colptr, int* perm, int* tgt_by_src,
@@ -219,6 +379,66 @@ extern "C" int gn_radius_fill(const float* pos, const int64_t* batch, int N, flo
     if (N == 0) return GN_OK;
     hipLaunchKernelGGL(gn::radius_fill_kernel, dim3((N + 127) / 128), dim3(128), 0, (hipStream_t)stream,
                        pos, batch, N, cutoff * cutoff, max_nbr, rowptr, E, edge_index, edge_vec, edge_diff);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+/* ---- periodic boundary conditions ---------------------------------------------------------------------------- */
+extern "C" int gn_cell_prepare(const float* cell, int n_mol, float* inv_cell, float* volume, void* stream) {
+    if (n_mol < 0 || (n_mol > 0 && (!cell || !inv_cell || !volume))) return GN_ERR_BAD_ARG;
+    if (n_mol == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::cell_prepare_kernel, dim3((n_mol + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                       cell, n_mol, inv_cell, volume);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_radius_count_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                   const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, int* deg,
+                                   void* stream) {
+    if (N < 0 || max_nbr <= 0 || n_mol < 0 || (N > 0 && (n_mol < 1 || !pos || !batch || !mol_ptr || !cell || !inv_cell || !deg)))
+        return GN_ERR_BAD_ARG;
+    if (N == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::radius_pbc_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                       pos, batch, mol_ptr, cell, inv_cell, N, n_mol, cutoff * cutoff, max_nbr, deg,
+                       (const int64_t*)nullptr, (int64_t)0, (int64_t*)nullptr, (int*)nullptr, (float*)nullptr, (float*)nullptr);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_radius_fill_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                  const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr,
+                                  const int64_t* rowptr, int64_t E, int64_t* edge_index, int* edge_shift,
+                                  float* edge_vec, float* edge_diff, void* stream) {
+    if (N < 0 || max_nbr <= 0 || E < 0 || n_mol < 0 || (N > 0 && (n_mol < 1 || !pos || !batch || !mol_ptr || !cell || !inv_cell || !rowptr)))
+        return GN_ERR_BAD_ARG;
+    if (E > 0 && (!edge_index || !edge_shift || !edge_vec || !edge_diff)) return GN_ERR_BAD_ARG;
+    if (N == 0 || E == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::radius_pbc_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                       pos, batch, mol_ptr, cell, inv_cell, N, n_mol, cutoff * cutoff, max_nbr, (int*)nullptr,
+                       rowptr, E, edge_index, edge_shift, edge_vec, edge_diff);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_edge_vectors_pbc(const float* pos, const int* src, const int* dst, const int* shift, const float* cell,
+                                   const int64_t* batch, int E, int n_mol, float* edge_vec, float* edge_diff, void* stream) {
+    if (E < 0 || n_mol < 0) return GN_ERR_BAD_ARG;
+    if (E == 0) return GN_OK;
+    if (n_mol < 1 || !pos || !src || !dst || !shift || !cell || !batch || !edge_vec || !edge_diff) return GN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(gn::edge_vectors_pbc_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       pos, src, dst, shift, cell, batch, E, n_mol, edge_vec, edge_diff);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_virial(const float* g_vec, const float* g_diff, const float* edge_vec, const int* rowptr,
+                         const int* mol_ptr, int n_mol, const float* volume, float* out, void* stream) {
+    if (n_mol < 0) return GN_ERR_BAD_ARG;
+    if (n_mol == 0) return GN_OK;
+    if (!rowptr || !mol_ptr || !volume || !out) return GN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(gn::virial_kernel, dim3(n_mol), dim3(256), 0, (hipStream_t)stream,
+                       g_vec, g_diff, edge_vec, rowptr, mol_ptr, volume, out);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }

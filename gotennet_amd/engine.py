@@ -387,8 +387,21 @@ class Graph:
         self.cut = torch.empty(E, **f32)
         self.perm = self.colptr = self.tgt_by_src = None
         self.edge_diff = self.edge_vec = None
+        #: periodic list (graph.distance_pbc): int32 [E, 3] lattice shifts, the int64 batch vector and the fp32 [n_mol, 3, 3]
+        #: cell (``set_periodic``); None for an isolated-molecule list
+        self.shift = self.batch = self.cell = None
         if edge_vec is not None:
             self.set_geometry(edge_diff, edge_vec)
+
+    def set_periodic(self, shift: torch.Tensor, batch: torch.Tensor, cell: torch.Tensor):
+        """Make this a periodic list: ``shift`` int32 [E, 3] in the order of the (target-major) edge list, ``batch`` int64 [N],
+        ``cell`` fp32 [n_mol, 3, 3] (rows = lattice vectors).  ``set_positions`` then uses gn_edge_vectors_pbc."""
+        if tuple(shift.shape) != (self.E, 3) or batch.shape[0] != self.N or cell.dim() != 3 or tuple(cell.shape[1:]) != (3, 3):
+            raise ValueError("set_periodic: shift [E, 3], batch [N] and cell [n_mol, 3, 3] expected")
+        self.shift = shift.to(torch.int32).contiguous()
+        self.batch = batch.to(torch.int64).contiguous()
+        self.cell = cell.detach().to(torch.float32).contiguous()
+        return self
 
     def set_geometry(self, edge_diff: torch.Tensor, edge_vec: torch.Tensor):
         """K1 on the current edge list: unit vectors, real harmonics, radial basis, cutoff."""
@@ -398,13 +411,23 @@ class Graph:
              cfg.lmax, cfg.R, cfg.basis, ptr(pw.rb0), ptr(pw.rb1), float(cfg.cutoff),
              ptr(self.rl), ptr(self.phi), ptr(self.cut), _stream())
 
-    def set_positions(self, pos: torch.Tensor):
-        """Edge vectors of the fixed edge list for new positions (gn_edge_vectors), then the geometry."""
+    def set_positions(self, pos: torch.Tensor, cell: Optional[torch.Tensor] = None):
+        """Edge vectors of the fixed edge list for new positions (gn_edge_vectors; gn_edge_vectors_pbc with the stored shifts
+        when the list is periodic, for ``cell`` -- fp32 contiguous [n_mol, 3, 3] -- or the graph's own), then the geometry."""
         if self.edge_vec is None:
             self.edge_vec = torch.empty((self.E, 3), dtype=torch.float32, device=pos.device)
             self.edge_diff = torch.empty(self.E, dtype=torch.float32, device=pos.device)
-        call("gn_edge_vectors", ptr(pos), ptr(self.src), ptr(self.dst), self.E, ptr(self.edge_vec), ptr(self.edge_diff),
-             _stream())
+        if self.shift is not None:
+            cell = self.cell if cell is None else cell
+            if cell.dtype != torch.float32 or not cell.is_contiguous() or tuple(cell.shape) != tuple(self.cell.shape):
+                raise ValueError(f"set_positions: cell must be contiguous fp32 {tuple(self.cell.shape)}")
+            call("gn_edge_vectors_pbc", ptr(pos), ptr(self.src), ptr(self.dst), ptr(self.shift), ptr(cell), ptr(self.batch),
+                 self.E, cell.shape[0], ptr(self.edge_vec), ptr(self.edge_diff), _stream())
+        elif cell is not None:
+            raise ValueError("set_positions: a cell was given but the graph has no shifts (set_periodic)")
+        else:
+            call("gn_edge_vectors", ptr(pos), ptr(self.src), ptr(self.dst), self.E, ptr(self.edge_vec), ptr(self.edge_diff),
+                 _stream())
         self.set_geometry(self.edge_diff, self.edge_vec)
 
     def csc(self):
@@ -1241,4 +1264,14 @@ def pos_gradient(g: Graph, g_vec: torch.Tensor, g_diff: torch.Tensor, sign: floa
     out = torch.empty((g.N, 3), dtype=torch.float32, device=g_vec.device)
     call("gn_pos_scatter", ptr(g_vec), ptr(g_diff), ptr(g.edge_vec), ptr(g.rowptr), ptr(colptr), ptr(perm),
          g.N, float(sign), ptr(out), _stream())
+    return out
+
+
+def virial(g: Graph, g_vec: torch.Tensor, g_diff: torch.Tensor, mol_ptr: torch.Tensor, n_mol: int,
+           volume: torch.Tensor) -> torch.Tensor:
+    """[n_mol, 3, 3]: (1 / volume[m]) sum_{e in box m} r_e (x) dE/dr_e, dE/dr_e = g_vec + g_diff r / |r| = (1/V) dE/d(strain)
+    (ASE's sign), as computed -- not symmetrised (gn_virial: fixed-order sums, bit-reproducible; an empty box gives zeros)."""
+    out = torch.empty((n_mol, 3, 3), dtype=torch.float32, device=g.rowptr.device)
+    call("gn_virial", ptr(g_vec), ptr(g_diff), ptr(g.edge_vec), ptr(g.rowptr), ptr(mol_ptr), n_mol, ptr(volume), ptr(out),
+         _stream())
     return out

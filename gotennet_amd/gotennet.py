@@ -47,15 +47,23 @@ class _RepresentationFn(torch.autograd.Function):
         return g_diff, g_vec, None, None, None
 
 
+def _radius_graph(net, pos, batch, cell):
+    """The wrapper's radius graph: ``graph.distance``, or ``graph.distance_pbc`` for a periodic call (``cell`` not None; the
+    lattice shifts are constants of the graph, so d edge_vec / d pos -- and gn_pos_scatter -- are what they are without)."""
+    from .graph import distance, distance_pbc
+    if cell is None:
+        return distance(pos, batch, net.cutoff, net.max_num_neighbors)
+    return distance_pbc(pos, batch, cell, net.cutoff, net.max_num_neighbors, check=False)[:3]   # (checked by the wrapper)
+
+
 class _RepresentationPosFn(torch.autograd.Function):
     """pos -> (h, X) including the radius graph (GotenNetWrapper.forward, gotennet.py:1043-1045)."""
 
     @staticmethod
-    def forward(ctx, pos, net, z32, batch):
-        from .graph import distance
+    def forward(ctx, pos, net, z32, batch, cell=None):
         cfg, pw = net.config(), net.packed_weights()
         cfg, key = net._dropout_call(cfg, z32.device)
-        edge_index, edge_diff, edge_vec = distance(pos.detach(), batch, net.cutoff, net.max_num_neighbors)
+        edge_index, edge_diff, edge_vec = _radius_graph(net, pos.detach(), batch, cell)
         g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff, edge_vec)
         h, X, tape = engine.forward(cfg, pw, z32, g, save=True, key=key)
         ctx.state = (cfg, pw, z32, g, tape)
@@ -65,7 +73,7 @@ class _RepresentationPosFn(torch.autograd.Function):
     def backward(ctx, gh, gX):
         cfg, pw, z32, g, tape = ctx.state
         g_vec, g_diff = engine.backward(cfg, pw, z32, g, tape, gh, gX)
-        return engine.pos_gradient(g, g_vec, g_diff, sign=1.0), None, None, None
+        return engine.pos_gradient(g, g_vec, g_diff, sign=1.0), None, None, None, None
 
 
 def refuse_second_order(what: str) -> None:
@@ -150,18 +158,17 @@ class _RepresentationPosParamFn(torch.autograd.Function):
     """(pos, *parameters) -> (h, X) including the radius graph, with parameter gradients."""
 
     @staticmethod
-    def forward(ctx, pos, net, z32, batch, cfg, pw, *params):
-        from .graph import distance
+    def forward(ctx, pos, net, z32, batch, cell, cfg, pw, *params):
         ctx.cfg, ctx.pw = cfg, pw
-        edge_index, edge_diff, edge_vec = distance(pos.detach(), batch, net.cutoff, net.max_num_neighbors)
+        edge_index, edge_diff, edge_vec = _radius_graph(net, pos.detach(), batch, cell)
         g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff, edge_vec)
         return _param_forward(ctx, net, z32, g, params)
 
     @staticmethod
     def backward(ctx, gh, gX):
-        g_vec, g_diff, pg = _param_backward(ctx, gh, gX, ctx.needs_input_grad[0], 6)
+        g_vec, g_diff, pg = _param_backward(ctx, gh, gX, ctx.needs_input_grad[0], 7)
         g_pos = engine.pos_gradient(ctx.state[3], g_vec, g_diff, sign=1.0) if ctx.needs_input_grad[0] else None
-        return (g_pos, None, None, None, None, None, *pg)
+        return (g_pos, None, None, None, None, None, None, *pg)
 
 
 def unpack_param_grads(net, packed: engine.PackedWeights, by_id: bool = False):
@@ -805,24 +812,42 @@ class GotenNet(nn.Module):
 
 
 class GotenNetWrapper(GotenNet):
-    """Reference gotennet.py:1013-1045: builds the radius graph from ``inputs.z/.pos/.batch``."""
+    """Reference gotennet.py:1013-1045: builds the radius graph from ``inputs.z/.pos/.batch``.
+
+    ``periodic`` (opt-in, default False: an ``inputs.cell`` is ignored): the graph is the minimum-image radius graph of
+    ``graph.distance_pbc`` for ``inputs.cell`` (fp32 [n_mol, 3, 3] or [3, 3], rows = lattice vectors), on every route (no
+    grad, ``pos.requires_grad``, ``parameter_grads``, both), so ``Atomwise(derivative="forces")`` and energy-loss training
+    work on periodic data unchanged.  A ``cell`` that requires grad is refused: stress comes from ``EnergyForces`` /
+    ``CapturedStep``, not from autograd."""
+
+    #: build the radius graph under periodic boundary conditions from ``inputs.cell``
+    periodic = False
 
     def __init__(self, *args, max_num_neighbors=32, **kwargs):
         super().__init__(*args, **kwargs)
         self.max_num_neighbors = max_num_neighbors
 
     def forward(self, inputs) -> Tuple[Tensor, Tensor]:
-        from .graph import distance
         atomic_numbers, pos, batch = inputs.z, inputs.pos, inputs.batch
+        cell = None
+        if self.periodic:                            # refused before any launch
+            cell = getattr(inputs, "cell", None)
+            if cell is None:
+                raise ValueError("GotenNetWrapper.periodic: inputs.cell is missing")
+            if cell.requires_grad:
+                raise ValueError("cell requires grad: autograd with respect to the cell is not supported (stress comes "
+                                 "from EnergyForces / CapturedStep)")
+            from .graph import check_cell
+            check_cell(cell, self.cutoff)            # one host read of the cell
         params = self._param_path()
         if params is not None:                       # refused before any launch (the radius graph below is one)
             self._check_inputs(atomic_numbers, torch.zeros((2, 0), dtype=torch.int64), pos.new_zeros(0), pos.new_zeros((0, 3)))
             cfg, pw = self._param_config()
             if pos.requires_grad:
-                return _RepresentationPosParamFn.apply(pos, self, atomic_numbers.to(torch.int32), batch, cfg, pw, *params)
+                return _RepresentationPosParamFn.apply(pos, self, atomic_numbers.to(torch.int32), batch, cell, cfg, pw, *params)
         if torch.is_grad_enabled() and pos.requires_grad:
             self._warn_if_training()
             self._check_inputs(atomic_numbers, torch.zeros((2, 0), dtype=torch.int64), pos.new_zeros(0), pos.new_zeros((0, 3)))
-            return _RepresentationPosFn.apply(pos, self, atomic_numbers.to(torch.int32), batch)
-        edge_index, edge_diff, edge_vec = distance(pos, batch, self.cutoff, self.max_num_neighbors)
+            return _RepresentationPosFn.apply(pos, self, atomic_numbers.to(torch.int32), batch, cell)
+        edge_index, edge_diff, edge_vec = _radius_graph(self, pos, batch, cell)
         return super().forward(atomic_numbers, edge_index, edge_diff, edge_vec, _sorted=True)   # radius graph is target-major

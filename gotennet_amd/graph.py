@@ -38,6 +38,100 @@ def distance(pos: torch.Tensor, batch: torch.Tensor, cutoff: float, max_num_neig
     return edge_index, edge_diff, edge_vec
 
 
+
+# ---------------------------------------------------------------------------------------- periodic boundary conditions
+# Conventions (include/gotennet_hip.h): ``cell`` fp32 [n_mol, 3, 3] (a [3, 3] cell is broadcast), ROWS are the lattice vectors,
+# one cell per entry of ``batch`` -- a "molecule" is a periodic box; ``edge_shift`` int32 [E, 3];
+# edge_vec[e] = pos[j] - pos[i] + edge_shift[e] @ cell[batch[i]].  Minimum image only.
+def cell_widths(cell: torch.Tensor) -> torch.Tensor:
+    """fp64 [n_mol, 3]: the perpendicular widths V / |a_j x a_k| of every cell (width k is the distance between the two faces
+    spanned by the other two lattice vectors).  Plain torch, CPU tensors welcome."""
+    c = cell.detach().to(torch.float64).reshape(-1, 3, 3)
+    a, b, cc = c[:, 0], c[:, 1], c[:, 2]
+    vol = (a * torch.cross(b, cc, dim=1)).sum(1).abs()
+    faces = torch.stack([torch.cross(b, cc, dim=1), torch.cross(cc, a, dim=1), torch.cross(a, b, dim=1)], dim=1)
+    return vol.unsqueeze(1) / faces.norm(dim=2)
+
+
+def check_cell(cell: torch.Tensor, cutoff: float) -> torch.Tensor:
+    """Raise ``ValueError`` unless every perpendicular width of every cell is at least ``2 * cutoff`` (the minimum-image
+    condition: at most one image of a pair inside the cutoff, no atom sees an image of itself).  On the host in fp64, from
+    one read of ``cell``; returns the widths."""
+    if cell.dim() not in (2, 3) or tuple(cell.shape[-2:]) != (3, 3):
+        raise ValueError("cell must be [n_mol, 3, 3] or [3, 3] (rows = lattice vectors)")
+    w = cell_widths(cell.detach().cpu())
+    if not bool(torch.isfinite(w).all()) or bool((w < 2.0 * float(cutoff)).any()):
+        m = int(torch.where(torch.isfinite(w), w, torch.full_like(w, -1.0)).min(dim=1).values.argmin())
+        raise ValueError(f"cell {m}: perpendicular widths {[round(float(x), 4) for x in w[m]]} are not all >= 2 * cutoff = "
+                         f"{2.0 * float(cutoff)}: only the minimum image is supported (one image per pair, no self-images)")
+    return w
+
+
+def broadcast_cell(cell: torch.Tensor, n_mol: int) -> torch.Tensor:
+    """fp32 contiguous [n_mol, 3, 3] (a [3, 3] cell repeated for every box)."""
+    cell = cell.detach().to(torch.float32)
+    if cell.dim() == 2:
+        cell = cell.unsqueeze(0).expand(n_mol, 3, 3)
+    if tuple(cell.shape) != (n_mol, 3, 3):
+        raise ValueError(f"cell must be [{n_mol}, 3, 3] or [3, 3], got {tuple(cell.shape)}")
+    return cell.contiguous()
+
+
+def cell_prepare(cell: torch.Tensor, inv_cell: Optional[torch.Tensor] = None, volume: Optional[torch.Tensor] = None):
+    """-> (inv_cell [n_mol, 3, 3], volume [n_mol]) of a contiguous fp32 [n_mol, 3, 3] cell (gn_cell_prepare; into the given
+    buffers when passed)."""
+    n_mol = cell.shape[0]
+    if inv_cell is None:
+        inv_cell, volume = torch.empty_like(cell), torch.empty(n_mol, dtype=torch.float32, device=cell.device)
+    call("gn_cell_prepare", ptr(cell), n_mol, ptr(inv_cell), ptr(volume), torch.cuda.current_stream().cuda_stream)
+    return inv_cell, volume
+
+
+def distance_pbc(pos: torch.Tensor, batch: torch.Tensor, cell: torch.Tensor, cutoff: float, max_num_neighbors: int = 32,
+                 n_mol: Optional[int] = None, check: bool = True):
+    """``distance`` under periodic boundary conditions -> (edge_index, edge_diff, edge_vec, edge_shift): the same neighbour
+    rule (target-major, sources ascending, strict d^2 < r^2 in fp32, the first ``max_num_neighbors`` sources, the self-loop
+    inside the cap) over the minimum images of each box's atoms; edge_shift int32 [E, 3] with
+    edge_vec = pos[j] - pos[i] + edge_shift @ cell[batch[i]].  Positions need not be wrapped into the cell.  ``batch`` must be
+    non-decreasing (each box's atoms contiguous, as for ``distance``): it is not checked here, and a target's sources are the
+    atom range of its box, so an unsorted vector gives a wrong list (in bounds, without an error).
+
+    Cells narrower than ``2 * cutoff`` raise ``ValueError`` before any radius-graph launch (``check_cell``: one host read of
+    ``cell``; the edge count is the other host read, as in ``distance``).  ``n_mol``: the number of boxes when a [3, 3] cell
+    is broadcast (default: read from the last entry of ``batch``).  ``check=False``: the caller has run ``check_cell`` on this
+    cell and cutoff already."""
+    if not pos.is_cuda:
+        raise GotenNetHipError("gotennet_amd.graph.distance_pbc runs on a ROCm device only (no CPU fallback)")
+    if cell.requires_grad:
+        raise ValueError("cell requires grad: autograd with respect to the cell is not supported (stress comes from "
+                         "EnergyForces / CapturedStep)")
+    if check:
+        check_cell(cell, cutoff)
+    from .outputs import molecule_ptr
+    pos = pos.detach().to(torch.float32).contiguous()
+    batch = batch.to(torch.int64).contiguous()
+    N = pos.shape[0]
+    if n_mol is None:
+        n_mol = cell.shape[0] if cell.dim() == 3 else (int(batch[-1].item()) + 1 if N else 0)
+    cell = broadcast_cell(cell.to(pos.device), n_mol)
+    st = torch.cuda.current_stream().cuda_stream
+    mol_ptr = molecule_ptr(batch, n_mol)
+    inv_cell, _ = cell_prepare(cell)
+    deg = torch.empty(N, dtype=torch.int32, device=pos.device)
+    call("gn_radius_count_pbc", ptr(pos), ptr(batch), ptr(mol_ptr), ptr(cell), ptr(inv_cell), N, n_mol, float(cutoff),
+         int(max_num_neighbors), ptr(deg), st)
+    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=pos.device)
+    torch.cumsum(deg, 0, out=rowptr[1:])
+    E = int(rowptr[-1].item()) if N else 0
+    edge_index = torch.empty((2, E), dtype=torch.int64, device=pos.device)
+    edge_shift = torch.empty((E, 3), dtype=torch.int32, device=pos.device)
+    edge_vec = torch.empty((E, 3), dtype=torch.float32, device=pos.device)
+    edge_diff = torch.empty(E, dtype=torch.float32, device=pos.device)
+    call("gn_radius_fill_pbc", ptr(pos), ptr(batch), ptr(mol_ptr), ptr(cell), ptr(inv_cell), N, n_mol, float(cutoff),
+         int(max_num_neighbors), ptr(rowptr), E, ptr(edge_index), ptr(edge_shift), ptr(edge_vec), ptr(edge_diff), st)
+    return edge_index, edge_diff, edge_vec, edge_shift
+
+
 class PaddedLayout:
     """Fixed sizes for a radius graph that is rebuilt on the device -- an MD step recorded into one hipGraph whose neighbour
     list changes (host work, once per trajectory: the molecule sizes are read here).  The layout only; the kernels that

@@ -9,7 +9,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import engine
+from . import engine, graph
 from .gotennet import GotenNet
 from .outputs import Atomwise, molecule_ptr
 
@@ -85,8 +85,19 @@ class EnergyForces:
     @torch.no_grad()
     def __call__(self, z: torch.Tensor, edge_index: torch.Tensor, edge_diff: torch.Tensor, edge_vec: torch.Tensor,
                  batch: torch.Tensor, n_mol: int, mol_ptr: Optional[torch.Tensor] = None,
-                 forces: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        """-> (energy [n_mol,1], forces [N,3])."""
+                 forces: bool = True, cell: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], ...]:
+        """-> (energy [n_mol,1], forces [N,3]), or with ``cell`` (energy, forces, stress [n_mol,3,3]); without ``forces``
+        the entries after the energy are None.
+
+        ``cell`` (fp32 [n_mol, 3, 3] or [3, 3], rows = lattice vectors): the edges are those of a periodic system
+        (``graph.distance_pbc``: ``edge_vec`` already carries the lattice shifts) and the call returns
+        (energy, forces, stress [n_mol, 3, 3]) with stress[m] = (1 / |det cell_m|) sum_{e in box m} r_e (x) dE/dr_e = (1/V) dE/d(strain),
+        ASE's sign, not symmetrised (None without ``forces``).  Energies and forces are those of the same call without
+        ``cell``.  A call with ``cell`` neither uses nor creates the recorded step of ``replay=True``: it runs eagerly (a
+        periodic MD loop records its step with ``CapturedStep(..., cell=, edge_shift=)``), and it leaves the count of consecutive calls that
+        decides when a call without ``cell`` records (``replay_after``) where it was."""
+        if cell is not None and cell.requires_grad:                # before any launch
+            raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
         rep = self.rep
         cfg, pw = rep.config(), rep.packed_weights()
         N = z.shape[0]
@@ -101,6 +112,13 @@ class EnergyForces:
                     raise ValueError("batch must be non-decreasing (each molecule's atoms contiguous)")
                 mol_ptr = molecule_ptr(batch, n_mol)
                 self._mol_ptr = (mkey, batch, mol_ptr) if mkey is not None else None
+        if cell is not None:
+            volume = graph.cell_prepare(graph.broadcast_cell(cell.to(z.device), n_mol))[1] if forces else None
+            hits = self._hits
+            g = self._graph(cfg, pw, N, edge_index, edge_diff, edge_vec, forces)
+            if self._hits:                           # a topology hit: the replay counter of the plain path does not move
+                self._hits = hits                    # (a miss has reset it, as any new topology does)
+            return self._step(cfg, pw, g, z.to(torch.int32), mol_ptr, n_mol, forces, volume=volume, periodic=True)
         gs = self._graph_state
         if self.replay and gs is not None and forces and self._replay_ok(gs, cfg, pw, N, edge_index, n_mol):
             return self._replay(gs, z, edge_diff, edge_vec, mol_ptr)
@@ -112,14 +130,17 @@ class EnergyForces:
             return self._replay(gs, z, edge_diff, edge_vec, mol_ptr)
         return self._step(cfg, pw, g, z32, mol_ptr, n_mol, forces)
 
-    def _step(self, cfg, pw, g, z32, mol_ptr, n_mol, forces):
+    def _step(self, cfg, pw, g, z32, mol_ptr, n_mol, forces, volume=None, periodic=False):
         h, X, tape = engine.forward(cfg, pw, z32, g, save=forces)
         e, y, pre1 = self.head.energy_raw(h, z32, mol_ptr, n_mol, mode=cfg.gemm_mode)
         if not forces:
-            return e, None
+            return (e, None, None) if periodic else (e, None)
         gh = self.head.grad_h_raw(pre1, cfg.F_model or cfg.F, mode=cfg.gemm_mode)
         g_vec, g_diff = engine.backward(cfg, pw, z32, g, tape, gh, None)
-        return e, engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
+        f = engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
+        if not periodic:
+            return e, f
+        return e, f, engine.virial(g, g_vec, g_diff, mol_ptr, n_mol, volume)
 
     # ---- hipGraph replay of the eager step on a cached topology --------------------------------------------------
     def _replay_ok(self, gs, cfg, pw, N, edge_index, n_mol) -> bool:
@@ -291,12 +312,32 @@ class CapturedStep:
         step = CapturedStep(EnergyForces(rep, head), z, edge_index, batch, n_mol)
         energy, forces = step(pos)          # views of static output buffers: copy them to keep them
 
+    Periodic systems: pass ``cell`` (fp32 [n_mol, 3, 3] or [3, 3], rows = lattice vectors) and the ``edge_shift`` of
+    ``graph.distance_pbc``.  The recorded step is then gn_cell_prepare -> gn_edge_vectors_pbc (the stored shifts, no image
+    search) -> the same step -> gn_virial, all kernel nodes of the one graph:
+
+        ei, ed, ev, sh = graph.distance_pbc(pos, batch, cell, cutoff)
+        step = CapturedStep(EnergyForces(rep, head), z, ei, batch, n_mol, cell=cell, edge_shift=sh)
+        energy, forces, stress = step(pos)                  # or step(pos, cell=new_cell): a barostat's move
+
+    A new cell is copied into the static buffer and the recorded inverse / volume kernel follows it; it is width-checked on
+    the host (``graph.check_cell``, one read of the cell) unless ``check_cell=False``.
+
     An inference tool: attention dropout is never applied (the recorded step is ``EnergyForces``' own).
     """
 
     def __init__(self, ef: EnergyForces, z: torch.Tensor, edge_index: torch.Tensor, batch: torch.Tensor, n_mol: int,
-                 warmup: int = 2):
+                 warmup: int = 2, cell: Optional[torch.Tensor] = None, edge_shift: Optional[torch.Tensor] = None,
+                 check_cell: bool = True):
+        if (cell is None) != (edge_shift is None):           # before any launch
+            raise ValueError("CapturedStep: a periodic step needs both cell and edge_shift (graph.distance_pbc returns the "
+                             "shifts); neither for isolated molecules")
+        if cell is not None and cell.requires_grad:
+            raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
         rep, head = ef.rep, ef.head
+        self.check_cell = bool(check_cell)
+        if cell is not None and self.check_cell:
+            graph.check_cell(cell, float(rep.cutoff))
         self.cfg, self.pw = rep.config(), rep.packed_weights()
         dev = z.device
         self.z32 = z.to(torch.int32)
@@ -310,8 +351,15 @@ class CapturedStep:
             if bits & 2:
                 raise ValueError(f"edge_index holds indices outside [0, {self.N})")
             if bits & 1:
-                edge_index = edge_index[:, torch.sort(edge_index[1], stable=True).indices].contiguous()
+                order = torch.sort(edge_index[1], stable=True).indices
+                edge_index = edge_index[:, order].contiguous()
+                edge_shift = edge_shift[order] if edge_shift is not None else None
         self.g = engine.Graph(self.cfg, self.pw, self.N, edge_index)
+        self.cell = self.inv_cell = self.volume = None
+        if cell is not None:                          # static buffers: the recorded kernels read these addresses
+            self.cell = graph.broadcast_cell(cell.to(dev), n_mol).clone()
+            self.inv_cell, self.volume = torch.empty_like(self.cell), torch.empty(n_mol, dtype=torch.float32, device=dev)
+            self.g.set_periodic(edge_shift.to(dev), batch.to(dev), self.cell)
         self.g.csc()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -321,19 +369,37 @@ class CapturedStep:
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph), torch.no_grad():
-            self.energy, self.forces = self._body()
+            out = self._body()
+        self.energy, self.forces = out[0], out[1]
+        self.stress = out[2] if self.cell is not None else None
 
     def _body(self):
         cfg, pw, g = self.cfg, self.pw, self.g
-        g.set_positions(self.pos)
+        if self.cell is not None:
+            graph.cell_prepare(self.cell, self.inv_cell, self.volume)
+            g.set_positions(self.pos, self.cell)
+        else:
+            g.set_positions(self.pos)
         h, X, tape = engine.forward(cfg, pw, self.z32, g, save=True)
         e, y, pre1 = self.head.energy_raw(h, self.z32, self.mol_ptr, self.n_mol, mode=cfg.gemm_mode)
         gh = self.head.grad_h_raw(pre1, cfg.F_model or cfg.F, mode=cfg.gemm_mode)
         g_vec, g_diff = engine.backward(cfg, pw, self.z32, g, tape, gh, None)
-        return e, engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
+        f = engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
+        if self.cell is None:
+            return e, f
+        return e, f, engine.virial(g, g_vec, g_diff, self.mol_ptr, self.n_mol, self.volume)
 
     @torch.no_grad()
-    def __call__(self, pos: torch.Tensor):
+    def __call__(self, pos: torch.Tensor, cell: Optional[torch.Tensor] = None):
+        """-> (energy, forces), or (energy, forces, stress) for a periodic step; ``cell``: a new cell for this and later steps."""
+        if cell is not None:
+            if self.cell is None:
+                raise ValueError("CapturedStep: this step was recorded without a cell")
+            if self.check_cell:
+                graph.check_cell(cell, float(self.cfg.cutoff))
+            self.cell.copy_(graph.broadcast_cell(cell.to(self.cell.device), self.n_mol))
         self.pos.copy_(pos)
         self.graph.replay()
-        return self.energy, self.forces
+        if self.cell is None:
+            return self.energy, self.forces
+        return self.energy, self.forces, self.stress

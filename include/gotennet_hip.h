@@ -489,6 +489,38 @@ int gn_radius_fill(const float* pos, const int64_t* batch, int N, float cutoff, 
 int gn_edge_vectors(const float* pos, const int* src, const int* dst, int E, float* edge_vec, float* edge_diff,
                     void* stream);
 
+/* ---- periodic boundary conditions: radius graph, fixed-list edge vectors, virial ---------------------------------
+ * Conventions: `cell` is fp32 [n_mol, 3, 3], its ROWS are the lattice vectors a, b, c, one cell per entry of `batch` (a
+ * "molecule" is a periodic box); `edge_shift` is int32 [E, 3]; edge_vec[e] = pos[j] - pos[i] + edge_shift[e] @ cell[batch[i]].
+ * Minimum image only: every perpendicular width V / |a_j x a_k| of every cell must be at least 2 * cutoff (checked by the
+ * caller on the host: graph.check_cell).  Each pair then has at most one image inside the cutoff, the one whose fractional
+ * coordinates all lie in (-1/2, 1/2): n_k = rintf(d . column k of inv_cell), d = pos[j] - pos[i], shift = -n.  No atom sees
+ * an image of itself; the self-loop (i, i, shift 0) stays, with edge_diff = 0.  Positions need not be wrapped into the cell.
+ * One device helper computes v = d + shift @ cell (fmaf in the order a, b, c) and |v|^2 (x, y, z) for the count, the fill
+ * and the fixed-list kernel: the three agree bit for bit.  mol_ptr [n_mol + 1] is gn_molecule_ptr's; batch entries outside
+ * [0, n_mol) are clamped (a wrong list, never an out-of-bounds access). */
+/* inv_cell [n_mol, 3, 3] = cell^-1 and volume [n_mol] = |det cell|, one thread per box (on the device, so a recorded step
+ * follows a changing cell). */
+int gn_cell_prepare(const float* cell, int n_mol, float* inv_cell, float* volume, void* stream);
+/* The neighbour rule of gn_radius_count / gn_radius_fill (target-major, sources ascending, strict d^2 < r^2 in fp32, the
+ * first max_nbr sources in source order, the self-loop counts against the cap) over the minimum images of a box's atoms.
+ * One wave64 per target: ballot + prefix popcount give each hit its slot, a running count applies the cap; deterministic,
+ * no atomics.  The fill also writes edge_shift. */
+int gn_radius_count_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                        const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, int* deg, void* stream);
+int gn_radius_fill_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                       const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, const int64_t* rowptr,
+                       int64_t E, int64_t* edge_index, int* edge_shift, float* edge_vec, float* edge_diff, void* stream);
+/* gn_edge_vectors for a periodic list: the stored shift, no image search; the arithmetic of gn_radius_fill_pbc. */
+int gn_edge_vectors_pbc(const float* pos, const int* src, const int* dst, const int* shift, const float* cell,
+                        const int64_t* batch, int E, int n_mol, float* edge_vec, float* edge_diff, void* stream);
+/* out[m] (3 x 3, row-major) = (1 / volume[m]) sum_{e in box m} r_e (x) dE/dr_e with dE/dr_e = g_vec[e] + g_diff[e] r_e / |r_e|
+ * (second term when g_diff != 0: gn_pos_scatter's expression) = (1/V) dE/d(strain), ASE's sign, not symmetrised.  Box m
+ * covers the edges rowptr[mol_ptr[m]] .. rowptr[mol_ptr[m + 1]] of a target-major list.  One workgroup per box, fixed-order
+ * sums, no atomics: identical inputs give identical bits; an empty box gives zeros. */
+int gn_virial(const float* g_vec, const float* g_diff, const float* edge_vec, const int* rowptr, const int* mol_ptr,
+              int n_mol, const float* volume, float* out, void* stream);
+
 /* ---- parameter gradients (first-order training: a loss on energies and / or (h, X)) -------------
  * Every reduction below runs in a fixed order and uses no atomics: identical inputs give identical bits. */
 /* dW = dY^T A and db = sum_r dY of a Dense product y = A W^T + b (layers.py:457-529): several independent problems in
