@@ -1,5 +1,8 @@
-// gn_gemm.h -- declarations shared by the exact-fp32 (gn_gemm.hip) and the 3xbf16-split
-// (gn_gemm_split.hip) projection kernels.
+// gn_gemm.h -- what the projection translation units share: the argument structs and the launchers (gn_gemm.hip: slab
+// kernel and entry points; gn_gemm_panel.hip; gn_gemm_colpipe.hip), the plane arithmetics (those three, the weight
+// preparation of gn_gemm_split.hip, and the MFMA loops of gn_wgrad.hip and gn_eqff_fused.hip), and the pieces the three
+// projection kernels have in common: the XCD cut of a tile list, the accumulator rescale, the three-term f16 product order
+// and the epilogue value chain.
 #pragma once
 #include "gn_common.h"
 
@@ -104,11 +107,55 @@ __device__ __forceinline__ int phys_row(const GemmArgs& p, int r) {
     return (r / p.row_cnt) * p.row_gstride + p.row_goff + (r % p.row_cnt);
 }
 
+// ---- pieces shared by the slab, the panel and the column-loop kernel -------------------------------------------------
+// XCD-aware order (block b runs on XCD b % 8, speed only): a list of T tiles is cut into 8 contiguous ranges and XCD x
+// walks range x, [lo, lo + cnt) -- tiles that share their A rows are pulled through ONE L2 instead of all eight.
+struct XcdCut { int lo, cnt; };
+__device__ __forceinline__ XcdCut xcd_cut(int T, int xcd) {
+    const int q = T >> 3, r = T & 7;
+    return {xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, q + (xcd < r ? 1 : 0)};
+}
 
+__device__ __forceinline__ float exp_scale(int e) { return __uint_as_float((unsigned)(127 - e) << 23); }   // 2^-e, e in [-120, 114]
 
-}  // namespace gn
+// the three-term product of two split operands, smallest terms first: lo*hi, hi*lo, hi*hi (lo*lo is below 2^-22 of the
+// product); term t multiplies plane F16_TA[t] of A with plane F16_TB[t] of the weight
+constexpr int F16_TA[3] = {1, 0, 0};
+constexpr int F16_TB[3] = {0, 1, 0};
 
-namespace gn {
+// The block exponents (four signed bytes: one per 8-row block of a 32-row MFMA tile, accumulator registers 4q..4q+3)
+// grew from e_old to e_new: bring the rows of `n` accumulator tiles along.  Exponents only grow: f <= 1, exact.
+__device__ __forceinline__ void rescale_rows(f32x16* acc, int n, unsigned e_old, unsigned e_new) {
+    asm volatile("" ::: "memory");                  // the caller's test is a real branch: never if-convert the multiplies
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float f = ldexpf(1.0f, (int)(signed char)(e_old >> (8 * q)) - (int)(signed char)(e_new >> (8 * q)));
+#pragma unroll
+        for (int t = 0; t < n; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[t][4 * q + r] *= f;
+    }
+}
+
+// The epilogue's value chain for one float4 of one output row at element offset `off`:
+//   x + bias -> pre_out -> activation (act: the column group lies in [act_lo, act_hi)) -> * gate or * act'(gate)
+//   -> + res -> C, non-temporally from column nt_store on (gn: the float4's first column).
+// rv / gv: the residual and gate values of that float4, loaded by the caller AHEAD of its stores, in an order that was
+// measured at each site.  (The slab kernel's residual / gate branch states the chain in place, see there.)  A site without a
+// gated / residual or non-temporal form (NT) passes nullptr / false and the compiler drops that link.  (float4s by reference,
+// the column test at the store: by value and with the test ahead of the call the column-loop kernel spilled, 10 % longer.)
+template <bool NT>
+__device__ __forceinline__ void epi_store(const float4& x, const float4& bias4, size_t off, float* C, float* pre_out, bool act,
+                                          int kind, const float* gate, int gate_mode, const float4& gv, const float* res,
+                                          const float4& rv, int gn, int nt_store) {
+    float4 v = x + bias4;
+    if (pre_out) st4(pre_out + off, v);
+    if (act) v = act4(v, kind);
+    if (gate) v = v * (gate_mode ? dact4(gv, kind) : gv);
+    if (res) v = rv + v;
+    if (NT && gn >= nt_store) st4_nt(C + off, v); else st4(C + off, v);
+}
+
 // ---- column-loop kernel (gn_gemm_colpipe.hip) -----------------------------------------------------------------------
 // Work decomposition: a UNIT is (row panel of 64, column pass of 128) of a problem, units are numbered panel-major.
 // Workgroup w of G takes the units [w T / G, (w + 1) T / G) (T = all units of the group): every workgroup gets the same MFMA
@@ -122,13 +169,26 @@ constexpr int CL_KC = 256;          // panel depth (one K chunk)
 // workgroup barrier for LDS hand-over that does NOT drain the vector-memory counter (a __syncthreads() waits for every
 // outstanding global store and load of the wave)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// ---- host: the launchers -------------------------------------------------------------------------------------------------
+// The kernel argument of a launch from its n <= GN_MAX_GROUP problems -- entries >= n repeat the last problem (never
+// selected), end[i] = the running count of BM x BN output tiles (units).  Returns the count of all tiles.
+template <class Args, class End>
+inline long fill_group(Args& a, End (&end)[GN_MAX_GROUP], const GemmArgs* g, int n, int BM, int BN) {
+    long run = 0;
+    for (int i = 0; i < GN_MAX_GROUP; ++i) {
+        a.g[i] = g[i < n ? i : n - 1];
+        if (i < n) run += (long)((g[i].M + BM - 1) / BM) * ((g[i].N + BN - 1) / BN);
+        end[i] = (End)run;
+    }
+    a.n = n;
+    return run;
+}
 }  // namespace gn
 
-// launcher for a group of n <= GN_MAX_GROUP problems (gn_gemm.hip).  split = 0: exact fp32 MFMA, W = fp32 [N][K];
-// split = 1: 3 x bf16-split MFMA, W = the fragment-major bf16 planes written by gn_split_bf16x3;
-// split = 2: 2 x fp16-split MFMA with block exponents, W = the planes (+ header) written by gn_split_f16x2
-int gn_gemm_launch(const gn::GemmArgs* g, int n, hipStream_t st, int split);
+// The two f16x2 kernels beside the slab kernel: their launchers take a validated group of n <= GN_MAX_GROUP problems with
+// rows (GemmArgs as gn_gemm.hip makes them, nt_store included; W = the planes (+ header) written by gn_split_f16x2).
 // the K-resident panel kernel for small f16x2 groups (gn_gemm_panel.hip): 1 = launched, 0 = does not apply, < 0 = -hipError_t
 int gn_gemm_panel_launch(const gn::GemmArgs* g, int n, hipStream_t st);
-// the column-loop kernel for large K = 256 f16x2 groups (gn_gemm_colpipe.hip; g[i].nt_store set by the caller): same return convention
+// the column-loop kernel for large K = 256 f16x2 groups (gn_gemm_colpipe.hip): same return convention
 int gn_gemm_colpipe_launch(const gn::GemmArgs* g, int n, hipStream_t st);

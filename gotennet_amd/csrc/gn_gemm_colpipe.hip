@@ -206,12 +206,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x2_colpipe(const ClArgs ca) {
                         if (!ok) continue;
                         const size_t off = (size_t)prow_e[i][q] * ldc + gn;
                         const int e = e_r[i][q];
-                        float4 v = make_float4(ldexpf(t[q].x, e), ldexpf(t[q].y, e), ldexpf(t[q].z, e), ldexpf(t[q].w, e)) + bias4;
-                        if (pre_out) st4(pre_out + off, v);
-                        if (act) v = act4(v, kind);
-                        if (gate) v = v * (gate_mode ? dact4(gv[q], kind) : gv[q]);
-                        if (res) v = rv[q] + v;
-                        if (gn >= nt_store) st4_nt(C + off, v); else st4(C + off, v);
+                        epi_store<true>(make_float4(ldexpf(t[q].x, e), ldexpf(t[q].y, e), ldexpf(t[q].z, e), ldexpf(t[q].w, e)), bias4, off,
+                                  C, pre_out, act, kind, gate, gate_mode, gv[q], res, rv[q], gn, nt_store);
                     }
                 }
             };
@@ -227,9 +223,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x2_colpipe(const ClArgs ca) {
                 for (int g = 0; g < NS; ++g) {
                     if (g + 1 < NS) read_a(g + 1, ab[(g + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
-                    // x = hi + lo per operand: lo*hi, hi*lo, hi*hi (lo*lo is below 2^-22 of the product); weights first: D^T
-                    constexpr int TA[3] = {1, 0, 0};
-                    constexpr int TB[3] = {0, 1, 0};
+                    // the three terms of gn_gemm.h; weights first: D^T
 #pragma unroll
                     for (int tt = 0; tt < 3; ++tt)
 #pragma unroll
@@ -239,10 +233,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x2_colpipe(const ClArgs ca) {
 #pragma unroll
                                 for (int r = 0; r < 16; ++r) z[r] = 0.f;
                                 acc[P][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                                    __builtin_bit_cast(f16x8, bq[g % NB][TB[tt]]), ab[g & 1][i][TA[tt]], z, 0, 0, 0);
+                                    __builtin_bit_cast(f16x8, bq[g % NB][F16_TB[tt]]), ab[g & 1][i][F16_TA[tt]], z, 0, 0, 0);
                             } else {
                                 acc[P][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                                    __builtin_bit_cast(f16x8, bq[g % NB][TB[tt]]), ab[g & 1][i][TA[tt]], acc[P][i], 0, 0, 0);
+                                    __builtin_bit_cast(f16x8, bq[g % NB][F16_TB[tt]]), ab[g & 1][i][F16_TA[tt]], acc[P][i], 0, 0, 0);
                             }
                         }
                     __builtin_amdgcn_sched_barrier(0);
@@ -287,17 +281,11 @@ int gn_gemm_colpipe_launch(const gn::GemmArgs* g, int n, hipStream_t st) {
     if (GN_CP_MIN_TILES < 0) return 0;
     gn::ClArgs ca;
     int n_max = 0;
-    long end = 0;
     for (int i = 0; i < n; ++i) {
         if (g[i].pro_mode != 0 || g[i].a_gate != nullptr || g[i].K != gn::CL_KC || g[i].a_seg != 0 || g[i].act_kind != GN_ACT_SILU) return 0;
         n_max = g[i].N > n_max ? g[i].N : n_max;
     }
-    for (int i = 0; i < gn::GN_MAX_GROUP; ++i) {
-        ca.g[i] = g[i < n ? i : n - 1];
-        if (i < n) end += (long)((g[i].M + 63) / 64) * ((g[i].N + 127) / 128);
-        ca.wend[i] = end;
-    }
-    ca.n = n;
+    const long end = gn::fill_group(ca, ca.wend, g, n, 64, 128);
     if (n_max < GN_CP_MIN_N || end < (long)GN_CP_MIN_TILES) return 0;
     const unsigned grid = (unsigned)(end < (long)GN_CP_GRID ? end : (long)GN_CP_GRID);
     hipLaunchKernelGGL(gn::gemm_f16x2_colpipe, dim3(grid), dim3(256), 0, st, ca);

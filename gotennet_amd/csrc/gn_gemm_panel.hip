@@ -39,18 +39,15 @@ __global__ __launch_bounds__(256) void gemm_f16x2_panel(const GroupArgs ga) {
     __shared__ __attribute__((aligned(16))) _Float16 panel[2 * APL];
     __shared__ int exps_w;                          // the four waves' block exponents (signed bytes)
 
-    // tile of this workgroup: the concatenated 32 x 128 tile list is cut into 8 contiguous ranges, XCD x (= blockIdx % 8)
-    // takes range x -- neighbouring column tiles share their A rows through one L2
+    // tile of this workgroup: ONE XCD cut (gn_gemm.h) of the concatenated 32 x 128 tile list -- neighbouring column tiles
+    // share their A rows through one L2
     int tiles_all = ga.tile_end[0];
 #pragma unroll
     for (int gi = 1; gi < GN_MAX_GROUP; ++gi)
         if (gi < ga.n) tiles_all = ga.tile_end[gi];
-    const int xcd = blockIdx.x & 7;
-    const int xq = tiles_all >> 3, xr = tiles_all & 7;
-    const int lo = xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq;
-    const int cnt = xq + (xcd < xr ? 1 : 0);
-    if ((int)(blockIdx.x >> 3) >= cnt) return;
-    const int t = lo + (int)(blockIdx.x >> 3);
+    const XcdCut cut = xcd_cut(tiles_all, blockIdx.x & 7);
+    if ((int)(blockIdx.x >> 3) >= cut.cnt) return;
+    const int t = cut.lo + (int)(blockIdx.x >> 3);
     // the problem this tile belongs to, read from the kernarg segment with ONE indexed scalar load (copying all four
     // descriptors and selecting cost ~500 scalar instructions before the first global load)
     int gi = 0, first = 0;
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(256) void gemm_f16x2_panel(const GroupArgs ga) {
         }
         need = need < -120 ? -120 : need;
         e_run = need > e_run ? need : e_run;
-        const float scale = __uint_as_float((unsigned)(127 - e_run) << 23);     // 2^-e_run
+        const float scale = exp_scale(e_run);
 #pragma unroll
         for (int ps = 0; ps < NPS; ++ps) {
             const int r = 8 * wave + ps * 2 + lr;
@@ -189,27 +186,17 @@ __global__ __launch_bounds__(256) void gemm_f16x2_panel(const GroupArgs ga) {
         // ahead in a second register set: slower at every size -- 254 VGPRs, [429 x 256 x 1536] 18.5 -> 19.4 us.)
         if (MULTI && ch + 1 < nch) fetch_chunk(ch + 1);
         const unsigned en = (unsigned)__builtin_amdgcn_readfirstlane(exps_w);
-        if (MULTI && __builtin_expect(en != e_acc && ch > 0, 0)) {               // the block exponents grew: bring the
-            asm volatile("" ::: "memory");                                     // accumulator rows along (exact: powers of two)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float f = ldexpf(1.0f, (int)(signed char)(e_acc >> (8 * q)) - (int)(signed char)(en >> (8 * q)));
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[4 * q + r] *= f;
-            }
-        }
+        if (MULTI && __builtin_expect(en != e_acc && ch > 0, 0)) rescale_rows(&acc, 1, e_acc, en);   // the block exponents grew
         e_acc = en;
 
-        // ---- k-steps off the panel: x = hi + lo per operand; lo*hi, hi*lo, hi*hi (lo*lo is below 2^-22 of the product)
+        // ---- k-steps off the panel: the three terms of gn_gemm.h
         const int g0 = ch * NS;
 #pragma unroll
         for (int g = 0; g < NS; ++g) {
-            const f16x8 ah = *reinterpret_cast<const f16x8*>(Ap + g * 16);
-            const f16x8 al = *reinterpret_cast<const f16x8*>(Ap + APL + g * 16);
-            const f16x8 bh = __builtin_bit_cast(f16x8, bq[g % NB][0]), bl = __builtin_bit_cast(f16x8, bq[g % NB][1]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+            const f16x8 a[2] = {*reinterpret_cast<const f16x8*>(Ap + g * 16), *reinterpret_cast<const f16x8*>(Ap + APL + g * 16)};
+#pragma unroll
+            for (int tt = 0; tt < 3; ++tt)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[F16_TA[tt]], __builtin_bit_cast(f16x8, bq[g % NB][F16_TB[tt]]), acc, 0, 0, 0);
             if (MULTI) { if (g0 + g + NB < ks_all) load_b(g0 + g + NB, bq[g % NB]); }
             else if (g + NB < NS) load_b(g + NB, bq[g % NB]);
         }
@@ -235,7 +222,7 @@ __global__ __launch_bounds__(256) void gemm_f16x2_panel(const GroupArgs ga) {
     bool ok[4];
     float4 rv[4], gv[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {                    // every residual / gate row requested before the first store
+    for (int u = 0; u < 4; ++u) {                    // every residual / gate row requested before the first store (measured)
         const int gm = m0 + u * RP + tid / C4;
         ok[u] = gm < p.M;
         off[u] = (size_t)phys_row(p, ok[u] ? gm : 0) * p.ldc + gn;
@@ -243,15 +230,10 @@ __global__ __launch_bounds__(256) void gemm_f16x2_panel(const GroupArgs ga) {
         gv[u] = (ok[u] && p.gate) ? ld4(p.gate + off[u]) : zero4();
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (!ok[u]) continue;
-        float4 v = ld4(&sc[(u * RP + tid / C4) * CP + cc]) + bias4;
-        if (p.pre_out) st4(p.pre_out + off[u], v);
-        if (act) v = act4(v, kind);
-        if (p.gate) v = v * (p.gate_mode ? dact4(gv[u], kind) : gv[u]);
-        if (p.res) v = rv[u] + v;
-        st4(p.C + off[u], v);
-    }
+    for (int u = 0; u < 4; ++u)
+        if (ok[u])
+            epi_store<false>(ld4(&sc[(u * RP + tid / C4) * CP + cc]), bias4, off[u], p.C, p.pre_out, act, kind, p.gate, p.gate_mode, gv[u],
+                      p.res, rv[u], gn, 0);
 }
 
 }  // namespace gn
@@ -264,7 +246,6 @@ __global__ __launch_bounds__(256) void gemm_f16x2_panel(const GroupArgs ga) {
 int gn_gemm_panel_launch(const gn::GemmArgs* g, int n, hipStream_t st) {
     if (GN_GEMM_PANEL_MAX <= 0) return 0;
     const int K = g[0].K;
-    gn::GroupArgs ga;
     bool silu = true, same = true, m256 = true;
     for (int i = 0; i < n; ++i) {
         if (g[i].pro_mode != 0 || g[i].a_gate != nullptr || (g[i].a_seg % 128) != 0) return 0;
@@ -275,27 +256,16 @@ int gn_gemm_panel_launch(const gn::GemmArgs* g, int n, hipStream_t st) {
     }
     const bool single = same && (K == 128 || K == 256 || K == 512);
     if (!single && !m256) return 0;
-    long end = 0;
-    for (int i = 0; i < gn::GN_MAX_GROUP; ++i) {
-        ga.g[i] = g[i < n ? i : n - 1];
-        ga.g[i].nt_store = 0x7fffffff;
-        if (i < n) end += (long)((g[i].M + 31) / 32) * ((g[i].N + 127) / 128);
-        ga.tile_end[i] = (int)end;
-    }
-    ga.n = n;
+    gn::GroupArgs ga;                                // (the kernel reads neither spread nor the problems' nt_store)
+    const long end = gn::fill_group(ga, ga.tile_end, g, n, 32, 128);
     ga.spread = 0;
     if (end == 0 || end > (long)GN_GEMM_PANEL_MAX) return 0;
-    const unsigned grid = (unsigned)(8L * ((end + 7) / 8));
-#define GN_PANEL_GO(NK_, MULTI_)                                                                                       \
-    do {                                                                                                              \
-        if (silu) hipLaunchKernelGGL((gn::gemm_f16x2_panel<NK_, MULTI_, true>), dim3(grid), dim3(256), 0, st, ga);     \
-        else hipLaunchKernelGGL((gn::gemm_f16x2_panel<NK_, MULTI_, false>), dim3(grid), dim3(256), 0, st, ga);         \
-    } while (0)
-    if (!single) GN_PANEL_GO(8, true);
-    else if (K == 128) GN_PANEL_GO(4, false);
-    else if (K == 256) GN_PANEL_GO(8, false);
-    else GN_PANEL_GO(16, false);
-#undef GN_PANEL_GO
+    void (*const k)(const gn::GroupArgs) =
+        !single ? (silu ? gn::gemm_f16x2_panel<8, true, true> : gn::gemm_f16x2_panel<8, true, false>)
+        : K == 128 ? (silu ? gn::gemm_f16x2_panel<4, false, true> : gn::gemm_f16x2_panel<4, false, false>)
+        : K == 256 ? (silu ? gn::gemm_f16x2_panel<8, false, true> : gn::gemm_f16x2_panel<8, false, false>)
+                   : (silu ? gn::gemm_f16x2_panel<16, false, true> : gn::gemm_f16x2_panel<16, false, false>);
+    hipLaunchKernelGGL(k, dim3((unsigned)(8L * ((end + 7) / 8))), dim3(256), 0, st, ga);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return -(int)e;
     return 1;

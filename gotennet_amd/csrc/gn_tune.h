@@ -79,6 +79,9 @@
 #ifndef GN_GEMM_BIG_CAP
 #define GN_GEMM_BIG_CAP 512    // persistent workgroups of the 128 x 128 slab kernel (two per CU)
 #endif
+#ifndef GN_SPLIT_MINW
+#define GN_SPLIT_MINW 2        // minimum waves per SIMD of the bf16x3 / f16x2 slab kernels (register cap 512 / n: two workgroups per CU)
+#endif
 #ifndef GN_GEMM_NT_MB
 #define GN_GEMM_NT_MB 100.0    // outputs of this many MiB and more are stored non-temporally ...
 #endif

@@ -44,6 +44,27 @@ def test_colpipe_and_edge_sized_epilogues(M, N, K):
     assert rel_err(C2, dd(res) + dd(A) @ dd(W).T) < 2e-6
 
 
+@pytest.mark.parametrize("K,mode", [(256, "f16x2"), (256, "split"), (256, "f32"), (512, "f16x2")])
+def test_non_temporal_store_branch(K, mode):
+    """The smallest output over the non-temporal threshold (100 MiB; M ragged against every tile height): columns below K stay
+    on the normal path, the rest are stored non-temporally -- column-loop kernel (K = 256, f16x2) and the slab kernel's big
+    tile (the other three); plain epilogue with bias and an activation range that straddles column 256."""
+    from gotennet_amd import engine
+    M, N = 17100, 1536
+    assert M * N * 4 >= 100 * 2 ** 20
+    g = torch.Generator(device="cuda").manual_seed(M + N + K)
+    r = _r(g)
+    A, W, b = r(M, K), r(N, K) / 8, r(N)
+    C = torch.empty(M, N, device="cuda")
+    lo, hi = 128, 640
+    engine.gemm(A, K, W, b, C, N, M, N, K, act=(lo, hi), mode=mode)
+    ref = A.double() @ W.double().T + b.double()
+    ref[:, lo:hi] = silu(ref[:, lo:hi])
+    err = rel_err(C, ref)
+    print(f"K {K} {mode}: {err:.3e}")
+    assert err < 2e-6
+
+
 def test_edge_sized_group_rowmap_segments():
     """A group as the step issues it: the edge-sized product with atom-sized riders of other shapes; row maps; the
     K-segmented A operand in whole chunks; a strided output (ldc > N, column offset)."""

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Projection launches at the atom-sized shapes of the step + the step itself, for the library GN_LIB_PATH selects:
    GN_LIB_PATH=gotennet_amd/variants/lib_nopanel.so python tools/panel_ab.py ; python tools/panel_ab.py
--> us per launch, max error against an fp64 product relative to max|C|, ms per energy+forces step (C2 batch, one molecule)."""
+-> us per launch, max error against an fp64 product relative to max|C|, ms per energy+forces step (C2 batch, one molecule).
+Arguments `shapes` / `steps` select one of the two parts (default: both)."""
 import os
 import sys
 import time
@@ -57,12 +58,14 @@ def shape(M, N, K, it=50, epi=False):
     print(f"[{tag}] gemm {M}x{N}x{K}{' +epi' if epi else ''}: {e0.elapsed_time(e1) * 1e3 / it:7.2f} us  err {err:.1e}")
 
 
-for s in ((2688, 512, 256), (2688, 256, 512), (2688, 256, 256), (2688, 1280, 256), (2688, 768, 256), (21504, 256, 256),
-          (21, 512, 256), (441, 1536, 256), (2688, 256, 128), (54368, 256, 256), (429, 256, 1536), (168, 256, 768),
-          (2688, 256, 1536), (2688, 256, 768), (21504, 256, 768), (5376, 1280, 256)):
-    shape(*s)
-shape(2688, 256, 256, epi=True)
-shape(54368, 256, 256, epi=True)
+what = sys.argv[1:] or ["shapes", "steps"]      # `python tools/panel_ab.py shapes`: the stand-alone launches only
+if "shapes" in what:
+    for s in ((2688, 512, 256), (2688, 256, 512), (2688, 256, 256), (2688, 1280, 256), (2688, 768, 256), (21504, 256, 256),
+              (21, 512, 256), (441, 1536, 256), (2688, 256, 128), (54368, 256, 256), (429, 256, 1536), (168, 256, 768),
+              (2688, 256, 1536), (2688, 256, 768), (21504, 256, 768), (5376, 1280, 256)):
+        shape(*s)
+    shape(2688, 256, 256, epi=True)
+    shape(54368, 256, 256, epi=True)
 
 
 def step(workload, B, lmax=2, n=20):
@@ -87,7 +90,8 @@ def step(workload, B, lmax=2, n=20):
     print(f"[{tag}] step {workload} b={B} lmax={lmax}: {best:.3f} ms  e[0] {float(e[0]):.6f} |f| {float(f.abs().sum()):.4f}")
 
 
-step("rmd17_aspirin", 128)
-step("rmd17_aspirin", 128, lmax=4, n=10)
-step("rmd17_aspirin", 1, n=50)
-step("rmd17_aspirin", 8, n=50)
+if "steps" in what:
+    step("rmd17_aspirin", 128)
+    step("rmd17_aspirin", 128, lmax=4, n=10)
+    step("rmd17_aspirin", 1, n=50)
+    step("rmd17_aspirin", 8, n=50)
