@@ -272,7 +272,7 @@ int gn_message_aggregate(const float* x, const float* v, int ldxv, const float* 
 
 /* ---- EQFF node chains as one kernel each (gotennet.py:716-748 after X_p = X W_vu^T) ------------------------------ */
 /* Forward: n = sqrt(sum_D X_p^2 + eps); [m1 | m2] = W_1 SiLU(W_0 [h | n] + b_0) + b_1; h += m1; X += m2 * X_p -- the
- * sequence gn_eqff_context -> gn_gemm(gamma_m.0) -> gn_gemm(gamma_m.1) -> gn_eqff_update as ONE launch (16 atoms per
+ * sequence gn_eqff_context -> gn_gemm(gamma_m.0) -> gn_gemm(gamma_m.1) -> gn_eqff_update as ONE launch (8 atoms per
  * workgroup, both products on MFMA in the plane arithmetics, W0p / W1p = planes written by gn_split_bf16x3 /
  * gn_split_f16x2 of gamma_m.0.weight [F, 2F] and gamma_m.1.weight [2F, F]).  ctx_out [N,2F], pre_out [N,F] (the
  * pre-activation of the hidden layer), mm_out [N,2F]: what the backward needs, or NULL.

@@ -14,7 +14,7 @@ TOL = 1e-4
 def test_eqff_fused_kernels_match_golden_and_sequence(name, mode):
     """gn_eqff_fused_forward / _backward (context -> gamma_m.0 -> gamma_m.1 -> update, and the input-gradient chain, one
     kernel each; reference gotennet.py:716-748) on the full-width fixtures (F = 128 and 256; N = 19 / 63 / 21: not a
-    multiple of the 16-atom tile): (h, X), energies and forces against the reference, and against the launch sequence
+    multiple of the 8-atom tile): (h, X), energies and forces against the reference, and against the launch sequence
     (`fuse_eqff = False`) within fp32 re-association."""
     from tests.test_hip_forces import _head_from_case
     from tests.test_hip_parity import _net_from_case
