@@ -109,6 +109,13 @@ SIGNATURES = {
     "gn_cell_prepare": [_P, _I, _P, _P, _P],
     "gn_radius_count_pbc": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P],
     "gn_radius_fill_pbc": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, C.c_int64, _P, _P, _P, _P, _P],
+    "gn_radius_count_pbc_images": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P],
+    "gn_radius_fill_pbc_images": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P, C.c_int64, _P, _P, _P, _P, _P],
+    "gn_edge_geometry_images": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P],
+    "gn_node_init_images": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P],
+    "gn_node_init_backward_images": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "gn_edge_geometry_backward_images": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _I, _P, _I, _P, _P, _P, _P],
+    "gn_embedding_grad_images": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gn_edge_vectors_pbc": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     "gn_virial": [_P, _P, _P, _P, _P, _I, _P, _P, _P],
     "gn_weight_grad_workspace": [_P, _I],

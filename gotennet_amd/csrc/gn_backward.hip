@@ -954,7 +954,7 @@ __global__ __launch_bounds__(256) void edge_init_bwd_kernel(
 __global__ __launch_bounds__(256) void node_init_bwd_kernel(
     const float* __restrict__ g_ctx, const int* __restrict__ z, const float* __restrict__ feat, int ldf,
     const float* __restrict__ cut, const float* __restrict__ A_nbr,
-    const int* __restrict__ rowptr, const int* __restrict__ src, int N, int F,
+    const int* __restrict__ rowptr, const int* __restrict__ src, int N, int F, const float* __restrict__ loop_dist,
     float* __restrict__ g_feat, float* __restrict__ g_cut) {
     const int i = xcd_item(blockIdx.x, N);
     if (i < 0) return;
@@ -964,7 +964,7 @@ __global__ __launch_bounds__(256) void node_init_bwd_kernel(
         const int j = src[e];
         float4 gfn = zero4();
         float gc = 0.f;
-        if (j != i) {
+        if (!self_loop(j, i, loop_dist, e)) {
             const float4 ga = gmi * ld4(A_nbr + (size_t)z[j] * F + c0);
             gfn = ga * cut[e];
             gc = hsum4(ga * ld4(feat + (size_t)e * ldf + c0));
@@ -1023,11 +1023,12 @@ __global__ __launch_bounds__(128) void edge_geometry_bwd_kernel(
     const float* __restrict__ vec, const float* __restrict__ dist, const int* __restrict__ src, const int* __restrict__ dst,
     int E, int R, int basis, const float* __restrict__ means, const float* __restrict__ betas, float cutoff, float alpha,
     const float* __restrict__ g_rl, int n_rl, const float* __restrict__ g_cut, int n_cut,
-    const float* __restrict__ g_phi, float* __restrict__ g_vec, float* __restrict__ g_diff) {
+    const float* __restrict__ g_phi, const float* __restrict__ loop_dist, float* __restrict__ g_vec,
+    float* __restrict__ g_diff) {
     constexpr int D = (LMAX + 1) * (LMAX + 1) - 1;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    if (src[e] == dst[e]) {          // self-loop: pos_i - pos_i and d = 0 are constants
+    if (self_loop(src[e], dst[e], loop_dist, e)) {          // self-loop: pos_i - pos_i and d = 0 are constants
         g_vec[3 * e] = g_vec[3 * e + 1] = g_vec[3 * e + 2] = 0.f;
         g_diff[e] = 0.f;
         return;
@@ -1421,15 +1422,21 @@ extern "C" int gn_edge_init_backward(const float* g_t0, const float* h, const fl
     return GN_OK;
 }
 
-extern "C" int gn_node_init_backward(const float* g_ctx, const int* z, const float* feat, int ldf, const float* cut,
-                                     const float* A_nbr, const int* rowptr, const int* src, int N, int F,
-                                     float* g_feat, float* g_cut, void* stream) {
+extern "C" int gn_node_init_backward_images(const float* g_ctx, const int* z, const float* feat, int ldf, const float* cut,
+                                            const float* A_nbr, const int* rowptr, const int* src, int N, int F,
+                                            const float* edge_diff, float* g_feat, float* g_cut, void* stream) {
     if (!bwd_dim_ok_wide(F) || N < 0 || (ldf & 3)) return GN_ERR_BAD_ARG;
     if (N == 0) return GN_OK;
     hipLaunchKernelGGL(gn::node_init_bwd_kernel, dim3(gn::xcd_grid(N)), dim3(256), 0, (hipStream_t)stream,
-                       g_ctx, z, feat, ldf, cut, A_nbr, rowptr, src, N, F, g_feat, g_cut);
+                       g_ctx, z, feat, ldf, cut, A_nbr, rowptr, src, N, F, edge_diff, g_feat, g_cut);
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+
+extern "C" int gn_node_init_backward(const float* g_ctx, const int* z, const float* feat, int ldf, const float* cut,
+                                     const float* A_nbr, const int* rowptr, const int* src, int N, int F,
+                                     float* g_feat, float* g_cut, void* stream) {
+    return gn_node_init_backward_images(g_ctx, z, feat, ldf, cut, A_nbr, rowptr, src, N, F, nullptr, g_feat, g_cut, stream);
 }
 
 extern "C" int gn_layernorm_silu_backward(const float* x, const float* gamma, const float* beta, float eps,
@@ -1452,18 +1459,36 @@ extern "C" int gn_layernorm_backward(const float* x, const float* gamma, float e
     return GN_OK;
 }
 
-extern "C" int gn_edge_geometry_backward(const float* edge_vec, const float* edge_diff, const int* src, const int* dst,
-                                         int E, int lmax, int R, int basis, const float* means, const float* betas,
-                                         float cutoff, const float* g_rl, int n_rl, const float* g_cut, int n_cut,
-                                         const float* g_phi, float* g_vec, float* g_diff, void* stream) {
+// loop_dist: the self-loop rule (gn_common.h self_loop)
+static int edge_geometry_backward(const float* edge_vec, const float* edge_diff, const int* src, const int* dst,
+                                  int E, int lmax, int R, int basis, const float* means, const float* betas,
+                                  float cutoff, const float* g_rl, int n_rl, const float* g_cut, int n_cut,
+                                  const float* g_phi, const float* loop_dist, float* g_vec, float* g_diff, void* stream) {
     if (E < 0 || lmax < 1 || lmax > 8 || R <= 0 || n_rl < 0 || n_cut < 0 || basis < 0 || basis > 2) return GN_ERR_BAD_ARG;
     if (E == 0) return GN_OK;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((E + 127) / 128), block(128);
     GN_SWITCH_LMAX(edge_geometry_bwd_kernel, grid, block, st, edge_vec, edge_diff, src, dst, E, R, basis, means, betas,
-                   cutoff, 5.0f / cutoff, g_rl, n_rl, g_cut, n_cut, g_phi, g_vec, g_diff);
+                   cutoff, 5.0f / cutoff, g_rl, n_rl, g_cut, n_cut, g_phi, loop_dist, g_vec, g_diff);
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+
+extern "C" int gn_edge_geometry_backward(const float* edge_vec, const float* edge_diff, const int* src, const int* dst,
+                                         int E, int lmax, int R, int basis, const float* means, const float* betas,
+                                         float cutoff, const float* g_rl, int n_rl, const float* g_cut, int n_cut,
+                                         const float* g_phi, float* g_vec, float* g_diff, void* stream) {
+    return edge_geometry_backward(edge_vec, edge_diff, src, dst, E, lmax, R, basis, means, betas, cutoff, g_rl, n_rl, g_cut,
+                                  n_cut, g_phi, nullptr, g_vec, g_diff, stream);
+}
+
+extern "C" int gn_edge_geometry_backward_images(const float* edge_vec, const float* edge_diff, const int* src, const int* dst,
+                                                int E, int lmax, int R, int basis, const float* means, const float* betas,
+                                                float cutoff, const float* g_rl, int n_rl, const float* g_cut, int n_cut,
+                                                const float* g_phi, float* g_vec, float* g_diff, void* stream) {
+    if (E > 0 && !edge_diff) return GN_ERR_BAD_ARG;
+    return edge_geometry_backward(edge_vec, edge_diff, src, dst, E, lmax, R, basis, means, betas, cutoff, g_rl, n_rl, g_cut,
+                                  n_cut, g_phi, edge_diff, g_vec, g_diff, stream);
 }
 
 extern "C" int gn_pos_scatter(const float* g_vec, const float* g_diff, const float* edge_vec,

@@ -22,6 +22,14 @@ int gn_htr_backward_general(const float* g_t_out, const float* pre_t, const floa
 
 namespace gn {
 
+// Is edge e = (j -> i) the self-loop?  loop_dist == nullptr: by index (a list without self-images: every entry point that
+// predates them).  loop_dist = edge_diff: by index AND zero distance -- an atom's own periodic image (j == i, shift != 0,
+// distance > 0; the *_images radius graph) is a real neighbour.  The pointer is a kernel argument: wave-uniform, and read
+// only on edges with j == i.
+__device__ __forceinline__ bool self_loop(int j, int i, const float* __restrict__ loop_dist, int e) {
+    return j == i && (loop_dist == nullptr || loop_dist[e] == 0.0f);
+}
+
 // sigmoid on the hardware transcendentals: v_exp_f32 (2^x) and v_rcp_f32, ~1 ulp each -- 4 VALU instead of the ~20 of
 // expf + an IEEE division.  Round-3 counters: the segment softmax was VALU-bound (1080 VALU instructions per wave, 23 of
 // its 29 us), SiLU / SiLU' are a quarter of the VALU work of the HTR and message backward passes.  Error: the argument

@@ -64,12 +64,12 @@ __global__ void out_degree_kernel(const int* __restrict__ src, int E, int* __res
 template <int LMAX>
 __global__ void edge_sh_kernel(const float* __restrict__ vec, const float* __restrict__ dist,
                                const int* __restrict__ src, const int* __restrict__ dst, int E, float cutoff,
-                               float* __restrict__ rl, float* __restrict__ cut) {
+                               const float* __restrict__ loop_dist, float* __restrict__ rl, float* __restrict__ cut) {
     constexpr int D = (LMAX + 1) * (LMAX + 1) - 1;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
     float x = vec[3 * e], y = vec[3 * e + 1], z = vec[3 * e + 2];
-    if (src[e] != dst[e]) {                       // gotennet.py:978-980
+    if (!self_loop(src[e], dst[e], loop_dist, e)) {          // gotennet.py:978-980
         const float n = sqrtf(x * x + y * y + z * z);
         x /= n; y /= n; z /= n;
     }
@@ -109,7 +109,8 @@ __global__ void edge_rbf_kernel(const float* __restrict__ dist, int E, int R, in
 __global__ __launch_bounds__(256) void node_init_kernel(
     const int* __restrict__ z, const int* __restrict__ rowptr, const int* __restrict__ src,
     const float* __restrict__ feat, int ldf, const float* __restrict__ cut,
-    const float* __restrict__ A_na, const float* __restrict__ A_nbr, int N, int F, float* __restrict__ ctx) {
+    const float* __restrict__ A_na, const float* __restrict__ A_nbr, int N, int F, const float* __restrict__ loop_dist,
+    float* __restrict__ ctx) {
     __shared__ __attribute__((aligned(16))) float red[1024];
     const int i = xcd_item(blockIdx.x, N);
     if (i < 0) return;
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256) void node_init_kernel(
     float4 acc = zero4();
     for (int e = e0 + slot; e < e1; e += ns) {
         const int j = src[e];
-        if (j == i) continue;                     // layers.py:1660-1664: self-loops dropped
+        if (self_loop(j, i, loop_dist, e)) continue;      // layers.py:1660-1664: self-loops dropped
         const float4 f = ld4(feat + (size_t)e * ldf + c0) * cut[e];
         acc = fma4(ld4(A_nbr + (size_t)z[j] * F + c0), f, acc);
     }
@@ -194,22 +195,23 @@ extern "C" int gn_out_degree(const int* src, int E, int* outdeg, void* stream) {
     return GN_OK;
 }
 
-extern "C" int gn_edge_geometry(const float* edge_vec, const float* edge_diff, const int* src, const int* dst, int E,
-                                int lmax, int R, int basis, const float* means, const float* betas, float cutoff,
-                                float* rl, float* phi, float* cut, void* stream) {
+// loop_dist: the self-loop rule of the unit-vector normalisation (gn_common.h self_loop)
+static int edge_geometry(const float* edge_vec, const float* edge_diff, const int* src, const int* dst, int E,
+                         int lmax, int R, int basis, const float* means, const float* betas, float cutoff,
+                         const float* loop_dist, float* rl, float* phi, float* cut, void* stream) {
     if (E < 0 || lmax < 1 || lmax > 8 || R <= 0 || basis < 0 || basis > 2) return GN_ERR_BAD_ARG;
     if (E == 0) return GN_OK;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((E + 255) / 256), block(256);
     switch (lmax) {
-        case 1: hipLaunchKernelGGL(gn::edge_sh_kernel<1>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, rl, cut); break;
-        case 2: hipLaunchKernelGGL(gn::edge_sh_kernel<2>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, rl, cut); break;
-        case 3: hipLaunchKernelGGL(gn::edge_sh_kernel<3>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, rl, cut); break;
-        case 4: hipLaunchKernelGGL(gn::edge_sh_kernel<4>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, rl, cut); break;
-        case 5: hipLaunchKernelGGL(gn::edge_sh_kernel<5>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, rl, cut); break;
-        case 6: hipLaunchKernelGGL(gn::edge_sh_kernel<6>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, rl, cut); break;
-        case 7: hipLaunchKernelGGL(gn::edge_sh_kernel<7>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, rl, cut); break;
-        default: hipLaunchKernelGGL(gn::edge_sh_kernel<8>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, rl, cut); break;
+        case 1: hipLaunchKernelGGL(gn::edge_sh_kernel<1>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, loop_dist, rl, cut); break;
+        case 2: hipLaunchKernelGGL(gn::edge_sh_kernel<2>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, loop_dist, rl, cut); break;
+        case 3: hipLaunchKernelGGL(gn::edge_sh_kernel<3>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, loop_dist, rl, cut); break;
+        case 4: hipLaunchKernelGGL(gn::edge_sh_kernel<4>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, loop_dist, rl, cut); break;
+        case 5: hipLaunchKernelGGL(gn::edge_sh_kernel<5>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, loop_dist, rl, cut); break;
+        case 6: hipLaunchKernelGGL(gn::edge_sh_kernel<6>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, loop_dist, rl, cut); break;
+        case 7: hipLaunchKernelGGL(gn::edge_sh_kernel<7>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, loop_dist, rl, cut); break;
+        default: hipLaunchKernelGGL(gn::edge_sh_kernel<8>, grid, block, 0, st, edge_vec, edge_diff, src, dst, E, cutoff, loop_dist, rl, cut); break;
     }
     GN_LAUNCH_CHECK();
     const size_t tot = (size_t)E * R;
@@ -219,15 +221,34 @@ extern "C" int gn_edge_geometry(const float* edge_vec, const float* edge_diff, c
     return GN_OK;
 }
 
-extern "C" int gn_node_init(const int* z, const int* rowptr, const int* src, const float* feat, int ldf,
-                            const float* cut, const float* A_na, const float* A_nbr,
-                            int N, int F, float* ctx, void* stream) {
+extern "C" int gn_edge_geometry(const float* edge_vec, const float* edge_diff, const int* src, const int* dst, int E,
+                                int lmax, int R, int basis, const float* means, const float* betas, float cutoff,
+                                float* rl, float* phi, float* cut, void* stream) {
+    return edge_geometry(edge_vec, edge_diff, src, dst, E, lmax, R, basis, means, betas, cutoff, nullptr, rl, phi, cut, stream);
+}
+
+extern "C" int gn_edge_geometry_images(const float* edge_vec, const float* edge_diff, const int* src, const int* dst, int E,
+                                       int lmax, int R, int basis, const float* means, const float* betas, float cutoff,
+                                       float* rl, float* phi, float* cut, void* stream) {
+    if (E > 0 && !edge_diff) return GN_ERR_BAD_ARG;
+    return edge_geometry(edge_vec, edge_diff, src, dst, E, lmax, R, basis, means, betas, cutoff, edge_diff, rl, phi, cut, stream);
+}
+
+extern "C" int gn_node_init_images(const int* z, const int* rowptr, const int* src, const float* feat, int ldf,
+                                   const float* cut, const float* A_na, const float* A_nbr,
+                                   int N, int F, const float* edge_diff, float* ctx, void* stream) {
     if (!feature_dim_ok(F) || N < 0 || (ldf & 3)) return GN_ERR_BAD_ARG;
     if (N == 0) return GN_OK;
     hipLaunchKernelGGL(gn::node_init_kernel, dim3(gn::xcd_grid(N)), dim3(256), 0, (hipStream_t)stream,
-                       z, rowptr, src, feat, ldf, cut, A_na, A_nbr, N, F, ctx);
+                       z, rowptr, src, feat, ldf, cut, A_na, A_nbr, N, F, edge_diff, ctx);
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+
+extern "C" int gn_node_init(const int* z, const int* rowptr, const int* src, const float* feat, int ldf,
+                            const float* cut, const float* A_na, const float* A_nbr,
+                            int N, int F, float* ctx, void* stream) {
+    return gn_node_init_images(z, rowptr, src, feat, ldf, cut, A_na, A_nbr, N, F, nullptr, ctx, stream);
 }
 
 extern "C" int gn_edge_init(const float* h, const int* rowptr, const int* src, const float* feat, int ldf,

@@ -170,9 +170,9 @@ __global__ void molecule_ptr_kernel(const int64_t* __restrict__ batch, int N, in
 // ================================================================================ periodic boundary conditions
 // Conventions (include/gotennet_hip.h): cell fp32 [n_mol, 3, 3], ROWS are the lattice vectors a, b, c, one cell per entry of
 // `batch` (a "molecule" is a periodic box); edge_shift int32 [E, 3]; edge_vec[e] = pos[j] - pos[i] + edge_shift[e] @ cell.
-// Minimum image only: the host refuses cells whose perpendicular widths are below 2 * cutoff, so each pair has at most one
-// image inside the cutoff and that image has all fractional coordinates in (-1/2, 1/2): rounding the fractional difference
-// finds it, for skewed cells too.
+// Minimum image (radius_pbc_kernel): the host sends it only cells whose perpendicular widths are at least 2 * cutoff, so
+// each pair has at most one image inside the cutoff and that image has all fractional coordinates in (-1/2, 1/2): rounding
+// the fractional difference finds it, for skewed cells too.  Narrower cells: radius_pbc_images_kernel below.
 struct Image {
     float vx, vy, vz, d2;
     int sx, sy, sz;
@@ -274,6 +274,78 @@ __global__ __launch_bounds__(256) void radius_pbc_kernel(const float* __restrict
     if (!FILL && lane == 0) deg[i] = cnt < max_nbr ? cnt : max_nbr;
 }
 
+// ---- several images per pair: cells narrower than 2 * cutoff (down to cutoff / 3).
+// The self-loop of such a list is the edge with j == i AND shift 0; an atom's own periodic image (j == i, shift != 0) is a
+// real neighbour at distance |s @ cell| > 0.
+__device__ __forceinline__ bool is_self_loop(int j, int i, const Image& im) { return j == i && (im.sx | im.sy | im.sz) == 0; }
+
+// One wave64 per target atom, as radius_pbc_kernel, over the candidates (source j, image t) of its box: the flattened index
+// q = (j - j0) * n_img + t_flat, t_flat = (tx * ny + ty) * nz + tz (tx slowest), candidate shift s = -rint(f) + (t - R) with
+// f the fractional difference of image_of (the same expression, so R = 0 IS the minimum-image kernel, bit for bit) and
+// R = img_range[box] the host's per-axis bound (gn_radius_count_pbc_images in the header: every image inside the cutoff has
+// |s_k + rint(f_k)| <= R_k).  Ascending q is: sources ascending, then shifts ascending lexicographically in (sx, sy, sz).
+// Ballot + popcount of the lower lanes + the running wave-uniform count place each hit and carry the cap across trips: the
+// first max_nbr hits in that order, no atomics.  (jb, tb) = candidate of lane 0 as (source offset, image index): 32-bit
+// throughout, no product of the box size and n_img is ever formed.  FILL as above: one body for count and fill.
+template <bool FILL>
+__global__ __launch_bounds__(256) void radius_pbc_images_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch,
+                                                                const int* __restrict__ mol_ptr, const float* __restrict__ cell,
+                                                                const float* __restrict__ inv_cell,
+                                                                const int* __restrict__ img_range, int N, int n_mol, float r2,
+                                                                int max_nbr, int* __restrict__ deg,
+                                                                const int64_t* __restrict__ rowptr, int64_t E,
+                                                                int64_t* __restrict__ edge_index, int* __restrict__ edge_shift,
+                                                                float* __restrict__ edge_vec, float* __restrict__ edge_diff) {
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= N) return;                                // (wave-uniform)
+    const int m = box_of(batch, i, n_mol);
+    const int j0 = mol_ptr[m], nj = mol_ptr[m + 1] - j0;
+    const float* c = cell + 9 * m;
+    const float* ic = inv_cell + 9 * m;
+    // (the host refuses R > GN_PBC_MAX_IMAGE_RANGE; clamped all the same: a bad array costs images, never a long loop)
+    const int Rx = min(max(img_range[3 * m], 0), GN_PBC_MAX_IMAGE_RANGE);
+    const int Ry = min(max(img_range[3 * m + 1], 0), GN_PBC_MAX_IMAGE_RANGE);
+    const int Rz = min(max(img_range[3 * m + 2], 0), GN_PBC_MAX_IMAGE_RANGE);
+    const int ny = 2 * Ry + 1, nz = 2 * Rz + 1, nyz = ny * nz, n_img = (2 * Rx + 1) * nyz;      // <= 343
+    const float pix = pos[3 * i], piy = pos[3 * i + 1], piz = pos[3 * i + 2];
+    const int64_t e0 = FILL ? rowptr[i] : 0;
+    int cnt = 0, jb = 0, tb = 0;
+    while (jb < nj && cnt < max_nbr) {
+        int t = tb + lane;                             // < n_img + 64
+        const int dj = t / n_img;
+        t -= dj * n_img;
+        const int j = j0 + jb + dj;
+        Image im;
+        bool hit = false;
+        if (jb + dj < nj) {
+            const int tx = t / nyz, r = t - tx * nyz, ty = r / nz, tz = r - ty * nz;
+            const float dx = pos[3 * j] - pix, dy = pos[3 * j + 1] - piy, dz = pos[3 * j + 2] - piz;
+            const int nx_ = (int)rintf(fmaf(dz, ic[6], fmaf(dy, ic[3], dx * ic[0])));
+            const int ny_ = (int)rintf(fmaf(dz, ic[7], fmaf(dy, ic[4], dx * ic[1])));
+            const int nz_ = (int)rintf(fmaf(dz, ic[8], fmaf(dy, ic[5], dx * ic[2])));
+            im = shifted(dx, dy, dz, tx - Rx - nx_, ty - Ry - ny_, tz - Rz - nz_, c);
+            hit = im.d2 < r2;                          // (the self-loop: 0 < r2)
+        }
+        const unsigned long long mask = __ballot(hit);
+        if (FILL && hit) {
+            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+            const int64_t e = e0 + slot;
+            if (slot < max_nbr && e < E) {
+                edge_index[e] = j;                     // row 0: source
+                edge_index[E + e] = i;                 // row 1: target
+                edge_shift[3 * e] = im.sx; edge_shift[3 * e + 1] = im.sy; edge_shift[3 * e + 2] = im.sz;
+                edge_vec[3 * e] = im.vx; edge_vec[3 * e + 1] = im.vy; edge_vec[3 * e + 2] = im.vz;
+                edge_diff[e] = is_self_loop(j, i, im) ? 0.0f : sqrtf(im.d2);
+            }
+        }
+        cnt += __popcll(mask);
+        tb += 64;                                      // the next 64 candidates
+        jb += tb / n_img;
+        tb %= n_img;
+    }
+    if (!FILL && lane == 0) deg[i] = cnt < max_nbr ? cnt : max_nbr;
+}
+
 // edge vectors of a FIXED periodic edge list for new positions / a new cell: the stored shift, no image search
 __global__ void edge_vectors_pbc_kernel(const float* __restrict__ pos, const int* __restrict__ src, const int* __restrict__ dst,
                                         const int* __restrict__ shift, const float* __restrict__ cell,
@@ -285,7 +357,7 @@ __global__ void edge_vectors_pbc_kernel(const float* __restrict__ pos, const int
     const float dx = pos[3 * j] - pos[3 * i], dy = pos[3 * j + 1] - pos[3 * i + 1], dz = pos[3 * j + 2] - pos[3 * i + 2];
     const Image im = shifted(dx, dy, dz, shift[3 * e], shift[3 * e + 1], shift[3 * e + 2], cell + 9 * box_of(batch, i, n_mol));
     edge_vec[3 * e] = im.vx; edge_vec[3 * e + 1] = im.vy; edge_vec[3 * e + 2] = im.vz;
-    edge_diff[e] = (j == i) ? 0.0f : sqrtf(im.d2);
+    edge_diff[e] = is_self_loop(j, i, im) ? 0.0f : sqrtf(im.d2);     // (an atom's own image, shift != 0, is a real edge)
 }
 
 // out[m] = (1 / volume[m]) sum_{e in box m} r_e (x) dE/dr_e,  dE/dr_e = g_vec + g_diff r / |r| (gn_pos_scatter's expression).
@@ -416,6 +488,40 @@ extern "C" int gn_radius_fill_pbc(const float* pos, const int64_t* batch, const 
     if (N == 0 || E == 0) return GN_OK;
     hipLaunchKernelGGL(gn::radius_pbc_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                        pos, batch, mol_ptr, cell, inv_cell, N, n_mol, cutoff * cutoff, max_nbr, (int*)nullptr,
+                       rowptr, E, edge_index, edge_shift, edge_vec, edge_diff);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+static bool radius_pbc_args_ok(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                               const float* inv_cell, const int* img_range, int N, int n_mol, int max_nbr) {
+    if (N < 0 || max_nbr <= 0 || n_mol < 0) return false;
+    return N == 0 || (n_mol >= 1 && pos && batch && mol_ptr && cell && inv_cell && img_range);
+}
+
+extern "C" int gn_radius_count_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                          const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff,
+                                          int max_nbr, int* deg, void* stream) {
+    if (!radius_pbc_args_ok(pos, batch, mol_ptr, cell, inv_cell, img_range, N, n_mol, max_nbr) || (N > 0 && !deg))
+        return GN_ERR_BAD_ARG;
+    if (N == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::radius_pbc_images_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                       pos, batch, mol_ptr, cell, inv_cell, img_range, N, n_mol, cutoff * cutoff, max_nbr, deg,
+                       (const int64_t*)nullptr, (int64_t)0, (int64_t*)nullptr, (int*)nullptr, (float*)nullptr, (float*)nullptr);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_radius_fill_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                         const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff,
+                                         int max_nbr, const int64_t* rowptr, int64_t E, int64_t* edge_index,
+                                         int* edge_shift, float* edge_vec, float* edge_diff, void* stream) {
+    if (!radius_pbc_args_ok(pos, batch, mol_ptr, cell, inv_cell, img_range, N, n_mol, max_nbr) || E < 0 || (N > 0 && !rowptr))
+        return GN_ERR_BAD_ARG;
+    if (E > 0 && (!edge_index || !edge_shift || !edge_vec || !edge_diff)) return GN_ERR_BAD_ARG;
+    if (N == 0 || E == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::radius_pbc_images_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                       pos, batch, mol_ptr, cell, inv_cell, img_range, N, n_mol, cutoff * cutoff, max_nbr, (int*)nullptr,
                        rowptr, E, edge_index, edge_shift, edge_vec, edge_diff);
     GN_LAUNCH_CHECK();
     return GN_OK;

@@ -354,14 +354,14 @@ static long wgrad_floats(const gn_wgrad_desc& d, int mode) {
 __global__ __launch_bounds__(256) void emb_source_kernel(
     const float* __restrict__ g_ctx, const float* __restrict__ feat, int ldf, const float* __restrict__ cut,
     const int* __restrict__ dst, const int* __restrict__ colptr, const int* __restrict__ perm, int N, int F,
-    float* __restrict__ P) {
+    const float* __restrict__ loop_dist, float* __restrict__ P) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)N * F) return;
     const int j = (int)(t / F), c = (int)(t % F);
     float acc = 0.f;
     for (int q = colptr[j]; q < colptr[j + 1]; ++q) {
         const int e = perm[q], i = dst[e];
-        if (i == j) continue;
+        if (self_loop(j, i, loop_dist, e)) continue;
         acc = fmaf(g_ctx[(long)i * 2 * F + F + c], feat[(long)e * ldf + c] * cut[e], acc);
     }
     P[t] = acc;
@@ -500,12 +500,20 @@ extern "C" int gn_weight_grad_group_mode(const gn_wgrad_desc* d, int n, int mode
 extern "C" int gn_embedding_grad(const float* g_ctx, const float* feat, int ldf, const float* cut, const int* dst,
                                  const int* colptr, const int* perm, const int* order, const int* sp_ptr, int n_species,
                                  int N, int F, float* work, float* dA_na, float* dA_nbr, void* stream) {
+    return gn_embedding_grad_images(g_ctx, feat, ldf, cut, dst, colptr, perm, order, sp_ptr, n_species, N, F, nullptr, work,
+                                    dA_na, dA_nbr, stream);
+}
+
+extern "C" int gn_embedding_grad_images(const float* g_ctx, const float* feat, int ldf, const float* cut, const int* dst,
+                                        const int* colptr, const int* perm, const int* order, const int* sp_ptr,
+                                        int n_species, int N, int F, const float* edge_diff, float* work, float* dA_na,
+                                        float* dA_nbr, void* stream) {
     if (N < 0 || F < 1 || n_species < 1 || ldf < 2 * F) return GN_ERR_BAD_ARG;
     const hipStream_t st = (hipStream_t)stream;
     const long nf = (long)N * F, sf = (long)n_species * F;
     if (nf > 0) {
         hipLaunchKernelGGL(gn::emb_source_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st,
-                           g_ctx, feat, ldf, cut, dst, colptr, perm, N, F, work);
+                           g_ctx, feat, ldf, cut, dst, colptr, perm, N, F, edge_diff, work);
         GN_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(gn::emb_species_kernel, dim3((unsigned)((sf + 255) / 256)), dim3(256), 0, st,

@@ -367,7 +367,8 @@ class Graph:
     replayed from a hipGraph, pipeline.CapturedStep)."""
 
     def __init__(self, cfg: Config, pw: PackedWeights, n_atoms: int, edge_index: torch.Tensor,
-                 edge_diff: Optional[torch.Tensor] = None, edge_vec: Optional[torch.Tensor] = None):
+                 edge_diff: Optional[torch.Tensor] = None, edge_vec: Optional[torch.Tensor] = None,
+                 self_images: bool = False):
         dev = edge_index.device
         E = edge_index.shape[1]
         self.N, self.E = n_atoms, E
@@ -390,6 +391,10 @@ class Graph:
         #: periodic list (graph.distance_pbc): int32 [E, 3] lattice shifts, the int64 batch vector and the fp32 [n_mol, 3, 3]
         #: cell (``set_periodic``); None for an isolated-molecule list
         self.shift = self.batch = self.cell = None
+        #: the list may hold self-images (an atom's own periodic image: src == dst, edge_diff > 0; graph.distance_pbc with
+        #: images="all"): the self-loop is then told by src == dst AND edge_diff == 0 (the gn_*_images entry points) instead
+        #: of src == dst.  On a list without self-images the two rules agree, bit for bit.
+        self.self_images = bool(self_images)
         if edge_vec is not None:
             self.set_geometry(edge_diff, edge_vec)
 
@@ -407,7 +412,7 @@ class Graph:
         """K1 on the current edge list: unit vectors, real harmonics, radial basis, cutoff."""
         cfg, pw = self.cfg, self.pw
         self.edge_diff, self.edge_vec = edge_diff, edge_vec
-        call("gn_edge_geometry", ptr(edge_vec), ptr(edge_diff), ptr(self.src), ptr(self.dst), self.E,
+        call("gn_edge_geometry_images" if self.self_images else "gn_edge_geometry", ptr(edge_vec), ptr(edge_diff), ptr(self.src), ptr(self.dst), self.E,
              cfg.lmax, cfg.R, cfg.basis, ptr(pw.rb0), ptr(pw.rb1), float(cfg.cutoff),
              ptr(self.rl), ptr(self.phi), ptr(self.cut), _stream())
 
@@ -569,8 +574,12 @@ def _init_forward(p: _Call, pw: PackedWeights, z32, new, tape: Optional[Tape], p
     feat = new(E, 2 * F_)
     gemm(g.phi, R, pw.Winit, pw.binit, feat, 2 * F_, E, 2 * F_, R)
     ctx0 = new(N, 2 * F_)
-    call("gn_node_init", ptr(z32), ptr(g.rowptr), ptr(g.src), ptr(feat), 2 * F_, ptr(g.cut),
-         ptr(pw.A_na), ptr(pw.A_nbr), N, F_, ptr(ctx0), st)
+    if g.self_images:
+        call("gn_node_init_images", ptr(z32), ptr(g.rowptr), ptr(g.src), ptr(feat), 2 * F_, ptr(g.cut),
+             ptr(pw.A_na), ptr(pw.A_nbr), N, F_, ptr(g.edge_diff), ptr(ctx0), st)
+    else:
+        call("gn_node_init", ptr(z32), ptr(g.rowptr), ptr(g.src), ptr(feat), 2 * F_, ptr(g.cut),
+             ptr(pw.A_na), ptr(pw.A_nbr), N, F_, ptr(ctx0), st)
     Fc = cfg.Fc or F_                              # (an embedded model keeps this intermediate compact: LayerNorm over the real channels)
     y_pre = new(N, Fc)
     gemm(ctx0, 2 * F_, pw.Wa, pw.ba, y_pre, Fc, N, Fc, 2 * F_)
@@ -1154,8 +1163,13 @@ def _init_backward(p: _Call, pw: PackedWeights, z32, tape: Tape, wb: _BackwardWo
     gy1 = new(N, Fc)
     call("gn_layernorm_silu_backward", ptr(tape.y_pre), ptr(pw.ln_w), ptr(pw.ln_b), 1e-5, ptr(gy), N, Fc, ptr(gy1), cfg.act, st)
     p.gemm(gy1, Fc, _T(pw, "Wa"), None, wb.g_ctx, 2 * F_, N, 2 * F_, Fc)
-    call("gn_node_init_backward", ptr(wb.g_ctx), ptr(z32), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(pw.A_nbr),
-         ptr(g.rowptr), ptr(g.src), N, F_, ptr(g_feat), wb.g_cut_parts.data_ptr() + 4 * E * wb.init_cut, st)
+    if g.self_images:
+        call("gn_node_init_backward_images", ptr(wb.g_ctx), ptr(z32), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(pw.A_nbr),
+             ptr(g.rowptr), ptr(g.src), N, F_, ptr(g.edge_diff), ptr(g_feat),
+             wb.g_cut_parts.data_ptr() + 4 * E * wb.init_cut, st)
+    else:
+        call("gn_node_init_backward", ptr(wb.g_ctx), ptr(z32), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(pw.A_nbr),
+             ptr(g.rowptr), ptr(g.src), N, F_, ptr(g_feat), wb.g_cut_parts.data_ptr() + 4 * E * wb.init_cut, st)
     return g_feat, gy, gy1
 
 
@@ -1174,8 +1188,13 @@ def _init_weight_grads(cfg, pw: PackedWeights, gw: PackedWeights, z32, g: Graph,
     sp_ptr = torch.searchsorted(zs, torch.arange(n_sp + 1, device=zs.device)).to(torch.int32)
     order = order.to(torch.int32)
     per_src = new(N, F_)                           # per-source sums of the A_nbr gradient (named: alive until the launch)
-    call("gn_embedding_grad", ptr(wb.g_ctx), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(g.dst), ptr(wb.colptr), ptr(wb.perm),
-         ptr(order), ptr(sp_ptr), n_sp, N, F_, ptr(per_src), ptr(gw.A_na), ptr(gw.A_nbr), _stream())
+    if g.self_images:
+        call("gn_embedding_grad_images", ptr(wb.g_ctx), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(g.dst), ptr(wb.colptr),
+             ptr(wb.perm), ptr(order), ptr(sp_ptr), n_sp, N, F_, ptr(g.edge_diff), ptr(per_src), ptr(gw.A_na), ptr(gw.A_nbr),
+             _stream())
+    else:
+        call("gn_embedding_grad", ptr(wb.g_ctx), ptr(tape.feat), 2 * F_, ptr(g.cut), ptr(g.dst), ptr(wb.colptr), ptr(wb.perm),
+             ptr(order), ptr(sp_ptr), n_sp, N, F_, ptr(per_src), ptr(gw.A_na), ptr(gw.A_nbr), _stream())
 
 
 def backward(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, tape: Tape,
@@ -1249,7 +1268,7 @@ def backward(cfg: Config, pw: PackedWeights, z32: torch.Tensor, g: Graph, tape: 
     g_phi = new(E, R)
     p.gemm(g_feat, 2 * F_, _T(pw, "Winit"), None, g_phi, R, E, R, 2 * F_)
     g_vec, g_diff = new(E, 3), new(E)
-    call("gn_edge_geometry_backward", ptr(g.edge_vec), ptr(g.edge_diff), ptr(g.src), ptr(g.dst), E, cfg.lmax, R,
+    call("gn_edge_geometry_backward_images" if g.self_images else "gn_edge_geometry_backward", ptr(g.edge_vec), ptr(g.edge_diff), ptr(g.src), ptr(g.dst), E, cfg.lmax, R,
          cfg.basis, ptr(pw.rb0), ptr(pw.rb1), float(cfg.cutoff), ptr(wb.g_rl_parts), wb.n_rl, ptr(wb.g_cut_parts), wb.n_cut,
          ptr(g_phi), ptr(g_vec), ptr(g_diff), p.st)
     if snap is not None:

@@ -30,10 +30,10 @@ class _RepresentationFn(torch.autograd.Function):
     (reference outputs.py:365-375 / goten_model.py:580-588)."""
 
     @staticmethod
-    def forward(ctx, edge_diff, edge_vec, net, z32, edge_index):
+    def forward(ctx, edge_diff, edge_vec, net, z32, edge_index, self_images=False):
         cfg, pw = net.config(), net.packed_weights()
         cfg, key = net._dropout_call(cfg, z32.device)
-        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff.detach(), edge_vec.detach())
+        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff.detach(), edge_vec.detach(), self_images=self_images)
         h, X, tape = engine.forward(cfg, pw, z32, g, save=True, key=key)
         ctx.state = (cfg, pw, z32, g, tape)
         return h, X
@@ -44,16 +44,20 @@ class _RepresentationFn(torch.autograd.Function):
         g_vec, g_diff = engine.backward(cfg, pw, z32, g, tape, gh, gX)
         # (an unsorted edge list was sorted with differentiable indexing in GotenNet.forward, so
         # autograd un-permutes these gradients itself)
-        return g_diff, g_vec, None, None, None
+        return g_diff, g_vec, None, None, None, None
 
 
-def _radius_graph(net, pos, batch, cell):
-    """The wrapper's radius graph: ``graph.distance``, or ``graph.distance_pbc`` for a periodic call (``cell`` not None; the
-    lattice shifts are constants of the graph, so d edge_vec / d pos -- and gn_pos_scatter -- are what they are without)."""
+def _radius_graph(net, pos, batch, periodic):
+    """The wrapper's radius graph -> (edge_index, edge_diff, edge_vec, self_images): ``graph.distance``, or
+    ``graph.distance_pbc`` for a periodic call (``periodic`` = (cell, image ranges or None), as the wrapper checked them; the
+    lattice shifts are constants of the graph, so d edge_vec / d pos -- and gn_pos_scatter -- are what they are without).
+    A multi-image list (ranges not None) may hold self-images: the graph built from it gets the flag."""
     from .graph import distance, distance_pbc
-    if cell is None:
-        return distance(pos, batch, net.cutoff, net.max_num_neighbors)
-    return distance_pbc(pos, batch, cell, net.cutoff, net.max_num_neighbors, check=False)[:3]   # (checked by the wrapper)
+    if periodic is None:
+        return (*distance(pos, batch, net.cutoff, net.max_num_neighbors), False)
+    cell, ranges = periodic
+    ei, ed, ev, _ = distance_pbc(pos, batch, cell, net.cutoff, net.max_num_neighbors, check=False, image_range=ranges)
+    return ei, ed, ev, ranges is not None
 
 
 class _RepresentationPosFn(torch.autograd.Function):
@@ -63,8 +67,8 @@ class _RepresentationPosFn(torch.autograd.Function):
     def forward(ctx, pos, net, z32, batch, cell=None):
         cfg, pw = net.config(), net.packed_weights()
         cfg, key = net._dropout_call(cfg, z32.device)
-        edge_index, edge_diff, edge_vec = _radius_graph(net, pos.detach(), batch, cell)
-        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff, edge_vec)
+        edge_index, edge_diff, edge_vec, self_images = _radius_graph(net, pos.detach(), batch, cell)
+        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff, edge_vec, self_images=self_images)
         h, X, tape = engine.forward(cfg, pw, z32, g, save=True, key=key)
         ctx.state = (cfg, pw, z32, g, tape)
         return h, X
@@ -142,16 +146,16 @@ class _RepresentationParamFn(torch.autograd.Function):
     """(edge_diff, edge_vec, *parameters) -> (h, X) with parameter gradients (``GotenNet.parameter_grads``)."""
 
     @staticmethod
-    def forward(ctx, edge_diff, edge_vec, net, z32, edge_index, cfg, pw, *params):
+    def forward(ctx, edge_diff, edge_vec, net, z32, edge_index, cfg, pw, self_images, *params):
         ctx.cfg, ctx.pw = cfg, pw
-        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff.detach(), edge_vec.detach())
+        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff.detach(), edge_vec.detach(), self_images=self_images)
         return _param_forward(ctx, net, z32, g, params)
 
     @staticmethod
     def backward(ctx, gh, gX):
         geometry = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        g_vec, g_diff, pg = _param_backward(ctx, gh, gX, geometry, 7)
-        return (g_diff, g_vec, None, None, None, None, None, *pg)
+        g_vec, g_diff, pg = _param_backward(ctx, gh, gX, geometry, 8)
+        return (g_diff, g_vec, None, None, None, None, None, None, *pg)
 
 
 class _RepresentationPosParamFn(torch.autograd.Function):
@@ -160,8 +164,8 @@ class _RepresentationPosParamFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, net, z32, batch, cell, cfg, pw, *params):
         ctx.cfg, ctx.pw = cfg, pw
-        edge_index, edge_diff, edge_vec = _radius_graph(net, pos.detach(), batch, cell)
-        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff, edge_vec)
+        edge_index, edge_diff, edge_vec, self_images = _radius_graph(net, pos.detach(), batch, cell)
+        g = engine.Graph(cfg, pw, z32.shape[0], edge_index, edge_diff, edge_vec, self_images=self_images)
         return _param_forward(ctx, net, z32, g, params)
 
     @staticmethod
@@ -783,8 +787,14 @@ class GotenNet(nn.Module):
             self._warned_inference_only = True
 
     def forward(self, atomic_numbers: Tensor, edge_index: Tensor, edge_diff: Tensor, edge_vec: Tensor,
-                _trace: Optional[list] = None, _sorted: Optional[bool] = None) -> Tuple[Tensor, Tensor]:
-        """``_sorted`` (internal): this CALL's edge list is target-major (the wrapper's own radius graph); None = the
+                _trace: Optional[list] = None, _sorted: Optional[bool] = None,
+                self_images: bool = False) -> Tuple[Tensor, Tensor]:
+        """``self_images``: the edge list may hold an atom's own periodic images (``graph.distance_pbc(images="all")`` on a
+        cell narrower than ``2 * cutoff``: ``src == dst`` with ``edge_diff`` > 0).  They are then neighbours like any other,
+        and the self-loop -- no NodeInit message, no unit-vector normalisation -- is the edge with ``src == dst`` AND
+        ``edge_diff == 0``.  Default False: the reference's rule, ``src == dst`` alone.
+
+        ``_sorted`` (internal): this CALL's edge list is target-major (the wrapper's own radius graph); None = the
         module's ``assume_sorted_edges``.  A per-call argument, not module state: calls from several threads do not race."""
         self._check_inputs(atomic_numbers, edge_index, edge_diff, edge_vec)
         params = self._param_path()
@@ -800,13 +810,13 @@ class GotenNet(nn.Module):
         z32 = atomic_numbers.to(torch.int32)
         if params is not None:
             cfg, pw = self._param_config()
-            return _RepresentationParamFn.apply(edge_diff, edge_vec, self, z32, edge_index, cfg, pw, *params)
+            return _RepresentationParamFn.apply(edge_diff, edge_vec, self, z32, edge_index, cfg, pw, bool(self_images), *params)
         self._warn_if_training()
         if torch.is_grad_enabled() and (edge_vec.requires_grad or edge_diff.requires_grad):
-            return _RepresentationFn.apply(edge_diff.contiguous(), edge_vec.contiguous(), self, z32, edge_index)
+            return _RepresentationFn.apply(edge_diff.contiguous(), edge_vec.contiguous(), self, z32, edge_index, bool(self_images))
         with torch.no_grad():
             cfg, key = self._dropout_call(cfg, z32.device)
-            g = engine.Graph(cfg, pw, N, edge_index, edge_diff, edge_vec)
+            g = engine.Graph(cfg, pw, N, edge_index, edge_diff, edge_vec, self_images=bool(self_images))
             h, X, _ = engine.forward(cfg, pw, z32, g, trace=_trace, key=key)
             return h, X
 
@@ -814,11 +824,13 @@ class GotenNet(nn.Module):
 class GotenNetWrapper(GotenNet):
     """Reference gotennet.py:1013-1045: builds the radius graph from ``inputs.z/.pos/.batch``.
 
-    ``periodic`` (opt-in, default False: an ``inputs.cell`` is ignored): the graph is the minimum-image radius graph of
+    ``periodic`` (opt-in, default False: an ``inputs.cell`` is ignored): the graph is the radius graph of
     ``graph.distance_pbc`` for ``inputs.cell`` (fp32 [n_mol, 3, 3] or [3, 3], rows = lattice vectors), on every route (no
     grad, ``pos.requires_grad``, ``parameter_grads``, both), so ``Atomwise(derivative="forces")`` and energy-loss training
-    work on periodic data unchanged.  A ``cell`` that requires grad is refused: stress comes from ``EnergyForces`` /
-    ``CapturedStep``, not from autograd."""
+    work on periodic data unchanged.  True (or "minimum"): the minimum image, cells narrower than ``2 * cutoff`` are
+    refused.  "all" / "auto": ``distance_pbc``'s ``images`` of that name -- several images per pair and self-images, cells
+    down to ``cutoff / 3`` wide (crystal unit cells), with the self-loop rule that goes with such lists.  A ``cell`` that
+    requires grad is refused: stress comes from ``EnergyForces`` / ``CapturedStep``, not from autograd."""
 
     #: build the radius graph under periodic boundary conditions from ``inputs.cell``
     periodic = False
@@ -837,8 +849,9 @@ class GotenNetWrapper(GotenNet):
             if cell.requires_grad:
                 raise ValueError("cell requires grad: autograd with respect to the cell is not supported (stress comes "
                                  "from EnergyForces / CapturedStep)")
-            from .graph import check_cell
-            check_cell(cell, self.cutoff)            # one host read of the cell
+            from .graph import resolve_images
+            # (one host read of the cell; the ranges are None for the minimum image)
+            cell = (cell, resolve_images(cell, self.cutoff, "minimum" if self.periodic is True else self.periodic))
         params = self._param_path()
         if params is not None:                       # refused before any launch (the radius graph below is one)
             self._check_inputs(atomic_numbers, torch.zeros((2, 0), dtype=torch.int64), pos.new_zeros(0), pos.new_zeros((0, 3)))
@@ -849,5 +862,6 @@ class GotenNetWrapper(GotenNet):
             self._warn_if_training()
             self._check_inputs(atomic_numbers, torch.zeros((2, 0), dtype=torch.int64), pos.new_zeros(0), pos.new_zeros((0, 3)))
             return _RepresentationPosFn.apply(pos, self, atomic_numbers.to(torch.int32), batch, cell)
-        edge_index, edge_diff, edge_vec = _radius_graph(self, pos, batch, cell)
-        return super().forward(atomic_numbers, edge_index, edge_diff, edge_vec, _sorted=True)   # radius graph is target-major
+        edge_index, edge_diff, edge_vec, self_images = _radius_graph(self, pos, batch, cell)
+        return super().forward(atomic_numbers, edge_index, edge_diff, edge_vec, _sorted=True,   # radius graph is target-major
+                               self_images=self_images)

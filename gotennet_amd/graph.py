@@ -42,7 +42,7 @@ def distance(pos: torch.Tensor, batch: torch.Tensor, cutoff: float, max_num_neig
 # ---------------------------------------------------------------------------------------- periodic boundary conditions
 # Conventions (include/gotennet_hip.h): ``cell`` fp32 [n_mol, 3, 3] (a [3, 3] cell is broadcast), ROWS are the lattice vectors,
 # one cell per entry of ``batch`` -- a "molecule" is a periodic box; ``edge_shift`` int32 [E, 3];
-# edge_vec[e] = pos[j] - pos[i] + edge_shift[e] @ cell[batch[i]].  Minimum image only.
+# edge_vec[e] = pos[j] - pos[i] + edge_shift[e] @ cell[batch[i]].
 def cell_widths(cell: torch.Tensor) -> torch.Tensor:
     """fp64 [n_mol, 3]: the perpendicular widths V / |a_j x a_k| of every cell (width k is the distance between the two faces
     spanned by the other two lattice vectors).  Plain torch, CPU tensors welcome."""
@@ -67,6 +67,44 @@ def check_cell(cell: torch.Tensor, cutoff: float) -> torch.Tensor:
     return w
 
 
+#: slack of the image range (``image_ranges``).  The kernel rounds the fractional difference f in fp32, so the image it
+#: centres the search on can be the second-nearest one when f lies within its rounding error of a half-integer:
+#: |f_k - rint(f_k)| <= 1/2 + err.  err is a few ulps of |f| times the condition number of the cell (f = d @ inv_cell with an
+#: fp32 inverse): below 1/64 for |f| * cond up to ~1e4, i.e. atoms unwrapped by thousands of cells.  A slack that is too
+#: large costs candidates, never edges; 1/64 keeps R = 0 for widths above 2.07 * cutoff and R <= 3 down to cutoff / 3.
+IMAGE_SLACK = 2.0 ** -6
+MAX_IMAGE_RANGE = 3          # GN_PBC_MAX_IMAGE_RANGE: at most 7^3 images per pair
+
+
+def image_ranges(cell: torch.Tensor, cutoff: float) -> torch.Tensor:
+    """The relaxed cell check of the multi-image radius graph -> R int32 [n_mol, 3] (CPU): per box and axis the range of
+    images around the rounded fractional difference that can hold a neighbour, R_k = floor(cutoff / w_k + 1/2 + IMAGE_SLACK)
+    with w_k the perpendicular width.  (An image vector v with fractional coordinate g_k along axis k has |v| >= |g_k| w_k,
+    and g_k = f_k - rint(f_k) + t_k with |f_k - rint(f_k)| <= 1/2: inside the cutoff means |t_k| < cutoff / w_k + 1/2.)
+    On the host in fp64, from one read of ``cell``.  Raises ``ValueError`` for a width that is not finite and positive or is
+    below ``cutoff / 3`` (R_k would exceed 3: more than 343 images per pair)."""
+    if cell.dim() not in (2, 3) or tuple(cell.shape[-2:]) != (3, 3):
+        raise ValueError("cell must be [n_mol, 3, 3] or [3, 3] (rows = lattice vectors)")
+    w = cell_widths(cell.detach().cpu())
+    ok = torch.isfinite(w) & (w > 0)
+    if not bool(ok.all()) or bool((w < float(cutoff) / 3.0).any()):
+        m = int(torch.where(ok, w, torch.full_like(w, -1.0)).min(dim=1).values.argmin())
+        raise ValueError(f"cell {m}: perpendicular widths {[round(float(x), 4) for x in w[m]]} are not all finite and >= "
+                         f"cutoff / 3 = {float(cutoff) / 3.0}: at most {2 * MAX_IMAGE_RANGE + 1} images per axis are searched")
+    return torch.floor(float(cutoff) / w + 0.5 + IMAGE_SLACK).to(torch.int32).clamp_(max=MAX_IMAGE_RANGE)
+
+
+def check_volume(cell: torch.Tensor) -> None:
+    """Raise ``ValueError`` unless every cell has a finite, non-zero volume: all a FIXED periodic edge list asks of a new cell
+    (its stored shifts stay valid while the cell deforms).  One host read of ``cell``."""
+    if cell.dim() not in (2, 3) or tuple(cell.shape[-2:]) != (3, 3):
+        raise ValueError("cell must be [n_mol, 3, 3] or [3, 3] (rows = lattice vectors)")
+    c = cell.detach().cpu().to(torch.float64).reshape(-1, 3, 3)
+    vol = (c[:, 0] * torch.cross(c[:, 1], c[:, 2], dim=1)).sum(1)          # a . (b x c), as cell_widths
+    if not bool(torch.isfinite(c).all()) or not bool(torch.isfinite(vol).all()) or bool((vol == 0).any()):
+        raise ValueError(f"cell volumes {[float(v) for v in vol]}: every cell needs a finite, non-zero volume")
+
+
 def broadcast_cell(cell: torch.Tensor, n_mol: int) -> torch.Tensor:
     """fp32 contiguous [n_mol, 3, 3] (a [3, 3] cell repeated for every box)."""
     cell = cell.detach().to(torch.float32)
@@ -87,26 +125,57 @@ def cell_prepare(cell: torch.Tensor, inv_cell: Optional[torch.Tensor] = None, vo
     return inv_cell, volume
 
 
+IMAGE_MODES = ("minimum", "auto", "all")
+
+
+def resolve_images(cell: torch.Tensor, cutoff: float, images: str) -> Optional[torch.Tensor]:
+    """The cell check of ``distance_pbc(images=)``, from ONE host read of ``cell`` -> None (the minimum-image kernels: every
+    box passed ``check_cell``) or the ``image_ranges`` array (the multi-image kernels).  Raises what those checks raise."""
+    if images not in IMAGE_MODES:
+        raise ValueError(f"images must be one of {IMAGE_MODES}, got {images!r}")
+    cell_host = cell.detach().cpu()
+    if images == "all":
+        return image_ranges(cell_host, cutoff)
+    try:
+        check_cell(cell_host, cutoff)
+        return None
+    except ValueError:
+        if images == "minimum":
+            raise
+    return image_ranges(cell_host, cutoff)
+
+
 def distance_pbc(pos: torch.Tensor, batch: torch.Tensor, cell: torch.Tensor, cutoff: float, max_num_neighbors: int = 32,
-                 n_mol: Optional[int] = None, check: bool = True):
+                 n_mol: Optional[int] = None, check: bool = True, images: str = "minimum",
+                 image_range: Optional[torch.Tensor] = None):
     """``distance`` under periodic boundary conditions -> (edge_index, edge_diff, edge_vec, edge_shift): the same neighbour
-    rule (target-major, sources ascending, strict d^2 < r^2 in fp32, the first ``max_num_neighbors`` sources, the self-loop
-    inside the cap) over the minimum images of each box's atoms; edge_shift int32 [E, 3] with
+    rule (target-major, sources ascending, strict d^2 < r^2 in fp32, the first ``max_num_neighbors`` hits, the self-loop
+    inside the cap) over the periodic images of each box's atoms; edge_shift int32 [E, 3] with
     edge_vec = pos[j] - pos[i] + edge_shift @ cell[batch[i]].  Positions need not be wrapped into the cell.  ``batch`` must be
     non-decreasing (each box's atoms contiguous, as for ``distance``): it is not checked here, and a target's sources are the
     atom range of its box, so an unsorted vector gives a wrong list (in bounds, without an error).
 
-    Cells narrower than ``2 * cutoff`` raise ``ValueError`` before any radius-graph launch (``check_cell``: one host read of
-    ``cell``; the edge count is the other host read, as in ``distance``).  ``n_mol``: the number of boxes when a [3, 3] cell
-    is broadcast (default: read from the last entry of ``batch``).  ``check=False``: the caller has run ``check_cell`` on this
-    cell and cutoff already."""
+    ``images`` selects the search:
+      "minimum" (default)  one image per pair.  Cells narrower than ``2 * cutoff`` raise ``ValueError`` before any
+                radius-graph launch (``check_cell``).
+      "all"     every image inside the cutoff (gn_radius_*_pbc_images): cells down to ``cutoff / 3`` wide
+                (``image_ranges``; narrower or non-finite ones raise ``ValueError`` before any launch).  Within a (target,
+                source) pair the images ascend lexicographically in the shift; the cap keeps a target's first hits in
+                (source, image) order.  An atom's own images are edges with ``src == dst`` and a non-zero shift,
+                ``edge_diff`` > 0: the self-loop is the edge with ``src == dst`` AND ``edge_diff == 0``, and whoever consumes
+                the list must use that rule (``EnergyForces(cell=)`` does; ``GotenNet.forward(self_images=True)``).
+                On cells of width >= ``2 * cutoff`` the result is the "minimum" list, bit for bit.
+      "auto"    "minimum" (same launches, same bits) when every box passes ``check_cell``, "all" for the whole batch otherwise.
+    Either way the host reads ``cell`` once and the edge count once, as ``distance`` reads the count.  ``n_mol``: the number
+    of boxes when a [3, 3] cell is broadcast (default: read from the last entry of ``batch``).  ``check=False``: the caller
+    has run ``resolve_images`` on this cell and cutoff and passes what it returned as ``image_range`` (None: the minimum
+    image); ``images`` is then not looked at and the cell is not read here."""
     if not pos.is_cuda:
         raise GotenNetHipError("gotennet_amd.graph.distance_pbc runs on a ROCm device only (no CPU fallback)")
     if cell.requires_grad:
         raise ValueError("cell requires grad: autograd with respect to the cell is not supported (stress comes from "
                          "EnergyForces / CapturedStep)")
-    if check:
-        check_cell(cell, cutoff)
+    ranges = resolve_images(cell, cutoff, images) if check else image_range
     from .outputs import molecule_ptr
     pos = pos.detach().to(torch.float32).contiguous()
     batch = batch.to(torch.int64).contiguous()
@@ -117,8 +186,13 @@ def distance_pbc(pos: torch.Tensor, batch: torch.Tensor, cell: torch.Tensor, cut
     st = torch.cuda.current_stream().cuda_stream
     mol_ptr = molecule_ptr(batch, n_mol)
     inv_cell, _ = cell_prepare(cell)
+    if ranges is None:
+        sfx, box = "", (ptr(cell), ptr(inv_cell))
+    else:
+        ranges = ranges.expand(n_mol, 3).contiguous().to(pos.device)
+        sfx, box = "_images", (ptr(cell), ptr(inv_cell), ptr(ranges))
     deg = torch.empty(N, dtype=torch.int32, device=pos.device)
-    call("gn_radius_count_pbc", ptr(pos), ptr(batch), ptr(mol_ptr), ptr(cell), ptr(inv_cell), N, n_mol, float(cutoff),
+    call("gn_radius_count_pbc" + sfx, ptr(pos), ptr(batch), ptr(mol_ptr), *box, N, n_mol, float(cutoff),
          int(max_num_neighbors), ptr(deg), st)
     rowptr = torch.zeros(N + 1, dtype=torch.int64, device=pos.device)
     torch.cumsum(deg, 0, out=rowptr[1:])
@@ -127,7 +201,7 @@ def distance_pbc(pos: torch.Tensor, batch: torch.Tensor, cell: torch.Tensor, cut
     edge_shift = torch.empty((E, 3), dtype=torch.int32, device=pos.device)
     edge_vec = torch.empty((E, 3), dtype=torch.float32, device=pos.device)
     edge_diff = torch.empty(E, dtype=torch.float32, device=pos.device)
-    call("gn_radius_fill_pbc", ptr(pos), ptr(batch), ptr(mol_ptr), ptr(cell), ptr(inv_cell), N, n_mol, float(cutoff),
+    call("gn_radius_fill_pbc" + sfx, ptr(pos), ptr(batch), ptr(mol_ptr), *box, N, n_mol, float(cutoff),
          int(max_num_neighbors), ptr(rowptr), E, ptr(edge_index), ptr(edge_shift), ptr(edge_vec), ptr(edge_diff), st)
     return edge_index, edge_diff, edge_vec, edge_shift
 

@@ -55,7 +55,7 @@ class EnergyForces:
         self._topo = self._mol_ptr = None
         self._hits, self._graph_state = 0, None
 
-    def _graph(self, cfg, pw, N, edge_index, edge_diff, edge_vec, need_csc):
+    def _graph(self, cfg, pw, N, edge_index, edge_diff, edge_vec, need_csc, self_images=False):
         key = None
         if self.cache_topology and not edge_index.is_inference():
             # (inference tensors -- a neighbour list built under torch.inference_mode() -- carry no version counter:
@@ -69,6 +69,7 @@ class EnergyForces:
         if hit:
             _, _, g, order = self._topo
             g.cfg = cfg                              # cutoff / eps may have changed under the same packed weights
+            g.self_images = self_images
             if order is not None:
                 edge_diff, edge_vec = edge_diff[order], edge_vec[order]
             g.set_geometry(edge_diff.contiguous(), edge_vec.contiguous())
@@ -76,7 +77,7 @@ class EnergyForces:
             ei, order = edge_index.contiguous(), None
             if self.check_edges:
                 ei, edge_diff, edge_vec, order = engine.sorted_edges(ei, edge_diff, edge_vec, N)
-            g = engine.Graph(cfg, pw, N, ei, edge_diff.contiguous(), edge_vec.contiguous())
+            g = engine.Graph(cfg, pw, N, ei, edge_diff.contiguous(), edge_vec.contiguous(), self_images=self_images)
             self._topo = (key, edge_index, g, order) if key is not None else None
         if need_csc:
             g.csc()
@@ -90,7 +91,8 @@ class EnergyForces:
         the entries after the energy are None.
 
         ``cell`` (fp32 [n_mol, 3, 3] or [3, 3], rows = lattice vectors): the edges are those of a periodic system
-        (``graph.distance_pbc``: ``edge_vec`` already carries the lattice shifts) and the call returns
+        (``graph.distance_pbc``, any ``images``: ``edge_vec`` already carries the lattice shifts; an atom's own images -- ``src == dst``
+        with ``edge_diff`` > 0 -- are neighbours, the self-loop is ``src == dst`` with ``edge_diff == 0``) and the call returns
         (energy, forces, stress [n_mol, 3, 3]) with stress[m] = (1 / |det cell_m|) sum_{e in box m} r_e (x) dE/dr_e = (1/V) dE/d(strain),
         ASE's sign, not symmetrised (None without ``forces``).  Energies and forces are those of the same call without
         ``cell``.  A call with ``cell`` neither uses nor creates the recorded step of ``replay=True``: it runs eagerly (a
@@ -115,7 +117,7 @@ class EnergyForces:
         if cell is not None:
             volume = graph.cell_prepare(graph.broadcast_cell(cell.to(z.device), n_mol))[1] if forces else None
             hits = self._hits
-            g = self._graph(cfg, pw, N, edge_index, edge_diff, edge_vec, forces)
+            g = self._graph(cfg, pw, N, edge_index, edge_diff, edge_vec, forces, self_images=True)
             if self._hits:                           # a topology hit: the replay counter of the plain path does not move
                 self._hits = hits                    # (a miss has reset it, as any new topology does)
             return self._step(cfg, pw, g, z.to(torch.int32), mol_ptr, n_mol, forces, volume=volume, periodic=True)
@@ -323,12 +325,17 @@ class CapturedStep:
     A new cell is copied into the static buffer and the recorded inverse / volume kernel follows it; it is width-checked on
     the host (``graph.check_cell``, one read of the cell) unless ``check_cell=False``.
 
+    ``images="all"`` (or "auto"): the list is a multi-image one (``graph.distance_pbc(images="all")``: cells down to
+    ``cutoff / 3`` wide, several images per pair, self-images).  The cell is then held to ``graph.image_ranges`` at
+    construction.  A fixed list's stored shifts stay valid while the cell deforms, so all a NEW cell has to have is a finite,
+    non-zero volume (``graph.check_volume``): the width conditions are conditions of the neighbour search, not of the step.
+
     An inference tool: attention dropout is never applied (the recorded step is ``EnergyForces``' own).
     """
 
     def __init__(self, ef: EnergyForces, z: torch.Tensor, edge_index: torch.Tensor, batch: torch.Tensor, n_mol: int,
                  warmup: int = 2, cell: Optional[torch.Tensor] = None, edge_shift: Optional[torch.Tensor] = None,
-                 check_cell: bool = True):
+                 check_cell: bool = True, images: str = "minimum"):
         if (cell is None) != (edge_shift is None):           # before any launch
             raise ValueError("CapturedStep: a periodic step needs both cell and edge_shift (graph.distance_pbc returns the "
                              "shifts); neither for isolated molecules")
@@ -336,8 +343,11 @@ class CapturedStep:
             raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
         rep, head = ef.rep, ef.head
         self.check_cell = bool(check_cell)
+        if images not in graph.IMAGE_MODES:
+            raise ValueError(f"images must be one of {graph.IMAGE_MODES}, got {images!r}")
+        self.images = images
         if cell is not None and self.check_cell:
-            graph.check_cell(cell, float(rep.cutoff))
+            graph.resolve_images(cell, float(rep.cutoff), images)
         self.cfg, self.pw = rep.config(), rep.packed_weights()
         dev = z.device
         self.z32 = z.to(torch.int32)
@@ -354,7 +364,7 @@ class CapturedStep:
                 order = torch.sort(edge_index[1], stable=True).indices
                 edge_index = edge_index[:, order].contiguous()
                 edge_shift = edge_shift[order] if edge_shift is not None else None
-        self.g = engine.Graph(self.cfg, self.pw, self.N, edge_index)
+        self.g = engine.Graph(self.cfg, self.pw, self.N, edge_index, self_images=cell is not None)
         self.cell = self.inv_cell = self.volume = None
         if cell is not None:                          # static buffers: the recorded kernels read these addresses
             self.cell = graph.broadcast_cell(cell.to(dev), n_mol).clone()
@@ -395,8 +405,10 @@ class CapturedStep:
         if cell is not None:
             if self.cell is None:
                 raise ValueError("CapturedStep: this step was recorded without a cell")
-            if self.check_cell:
+            if self.check_cell and self.images == "minimum":
                 graph.check_cell(cell, float(self.cfg.cutoff))
+            elif self.check_cell:
+                graph.check_volume(cell)
             self.cell.copy_(graph.broadcast_cell(cell.to(self.cell.device), self.n_mol))
         self.pos.copy_(pos)
         self.graph.replay()

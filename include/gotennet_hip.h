@@ -492,8 +492,9 @@ int gn_edge_vectors(const float* pos, const int* src, const int* dst, int E, flo
 /* ---- periodic boundary conditions: radius graph, fixed-list edge vectors, virial ---------------------------------
  * Conventions: `cell` is fp32 [n_mol, 3, 3], its ROWS are the lattice vectors a, b, c, one cell per entry of `batch` (a
  * "molecule" is a periodic box); `edge_shift` is int32 [E, 3]; edge_vec[e] = pos[j] - pos[i] + edge_shift[e] @ cell[batch[i]].
- * Minimum image only: every perpendicular width V / |a_j x a_k| of every cell must be at least 2 * cutoff (checked by the
- * caller on the host: graph.check_cell).  Each pair then has at most one image inside the cutoff, the one whose fractional
+ * gn_radius_count_pbc / gn_radius_fill_pbc look at the minimum image only: every perpendicular width V / |a_j x a_k| of every
+ * cell must be at least 2 * cutoff (checked by the caller on the host: graph.check_cell); narrower cells go to the *_images
+ * entry points below.  Each pair then has at most one image inside the cutoff, the one whose fractional
  * coordinates all lie in (-1/2, 1/2): n_k = rintf(d . column k of inv_cell), d = pos[j] - pos[i], shift = -n.  No atom sees
  * an image of itself; the self-loop (i, i, shift 0) stays, with edge_diff = 0.  Positions need not be wrapped into the cell.
  * One device helper computes v = d + shift @ cell (fmaf in the order a, b, c) and |v|^2 (x, y, z) for the count, the fill
@@ -511,7 +512,30 @@ int gn_radius_count_pbc(const float* pos, const int64_t* batch, const int* mol_p
 int gn_radius_fill_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
                        const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, const int64_t* rowptr,
                        int64_t E, int64_t* edge_index, int* edge_shift, float* edge_vec, float* edge_diff, void* stream);
-/* gn_edge_vectors for a periodic list: the stored shift, no image search; the arithmetic of gn_radius_fill_pbc. */
+/* Several images per pair: cells narrower than 2 * cutoff, where a pair has more than one image inside the cutoff and an atom
+ * sees images of itself.  The rule above, extended: within a (target, source) pair the images ascend lexicographically in
+ * (sx, sy, sz) -- a lattice vector added to both atoms moves every image of the pair alike, so wrapping does not change
+ * the order; the first max_nbr hits of a target in (source, image) order are kept.  The self-loop is the edge j == i with
+ * shift 0: always a hit, inside the cap, edge_diff exactly 0.  An atom's own image (j == i, shift != 0) is an ordinary edge
+ * with edge_diff = sqrtf(d^2) > 0.  d^2 comes from the helper the minimum-image and the fixed-list kernels use: a stored and a
+ * searched shift give the same bits, and on cells of width >= 2 * cutoff the list is gn_radius_fill_pbc's, bit for bit.
+ * img_range int32 [n_mol, 3]: R_k per box and axis; the candidates of a pair are s_k = -rintf(f_k) + t_k, t_k in [-R_k, R_k],
+ * f = d @ inv_cell.  An image inside the cutoff has |(f_k + s_k) w_k| < cutoff (w_k: perpendicular width), and
+ * |f_k - rint(f_k)| <= 1/2, so |t_k| < cutoff / w_k + 1/2: the caller passes R_k = floor(cutoff / w_k + 1/2 + slack), computed
+ * in fp64, the slack covering the fp32 error of f (graph.image_ranges: 1/64).  R_k > GN_PBC_MAX_IMAGE_RANGE (a width below
+ * about cutoff / 3) is for the caller to refuse; the kernel clamps it.  One wave64 per target over the flattened
+ * (source, image) candidates; ballot + prefix popcount + a running count, no atomics: deterministic.  Count and fill are
+ * one templated body. */
+#define GN_PBC_MAX_IMAGE_RANGE 3      /* at most 7^3 = 343 images per pair */
+int gn_radius_count_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                               const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff, int max_nbr,
+                               int* deg, void* stream);
+int gn_radius_fill_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                              const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff, int max_nbr,
+                              const int64_t* rowptr, int64_t E, int64_t* edge_index, int* edge_shift, float* edge_vec,
+                              float* edge_diff, void* stream);
+/* gn_edge_vectors for a periodic list: the stored shift, no image search; the arithmetic of gn_radius_fill_pbc.  edge_diff
+ * is exactly 0 on the self-loop (j == i and shift 0) only. */
 int gn_edge_vectors_pbc(const float* pos, const int* src, const int* dst, const int* shift, const float* cell,
                         const int64_t* batch, int E, int n_mol, float* edge_vec, float* edge_diff, void* stream);
 /* out[m] (3 x 3, row-major) = (1 / volume[m]) sum_{e in box m} r_e (x) dE/dr_e with dE/dr_e = g_vec[e] + g_diff[e] r_e / |r_e|
@@ -520,6 +544,26 @@ int gn_edge_vectors_pbc(const float* pos, const int* src, const int* dst, const 
  * sums, no atomics: identical inputs give identical bits; an empty box gives zeros. */
 int gn_virial(const float* g_vec, const float* g_diff, const float* edge_vec, const int* rowptr, const int* mol_ptr,
               int n_mol, const float* volume, float* out, void* stream);
+/* Edge lists with self-images (the *_images radius graph): the five kernels that single out the self-loop -- the unit-vector
+ * normalisation of gn_edge_geometry, the NodeInit sum and its backward, gn_edge_geometry_backward, the neighbour-embedding
+ * gradient -- tell it by `src == dst AND edge_diff == 0` instead of `src == dst`.  On a list without self-images the two rules
+ * pick the same edges and the results are the same bits.  Same arguments as the entry points they are named after, plus
+ * edge_diff [E] where those do not receive it. */
+int gn_edge_geometry_images(const float* edge_vec, const float* edge_diff, const int* src, const int* dst, int E,
+                            int lmax, int R, int basis, const float* means, const float* betas, float cutoff,
+                            float* rl, float* phi, float* cut, void* stream);
+int gn_node_init_images(const int* z, const int* rowptr, const int* src, const float* feat, int ldf, const float* cut,
+                        const float* A_na, const float* A_nbr, int N, int F, const float* edge_diff, float* ctx, void* stream);
+int gn_node_init_backward_images(const float* g_ctx, const int* z, const float* feat, int ldf, const float* cut,
+                                 const float* A_nbr, const int* rowptr, const int* src, int N, int F,
+                                 const float* edge_diff, float* g_feat, float* g_cut, void* stream);
+int gn_edge_geometry_backward_images(const float* edge_vec, const float* edge_diff, const int* src, const int* dst,
+                                     int E, int lmax, int R, int basis, const float* means, const float* betas,
+                                     float cutoff, const float* g_rl, int n_rl, const float* g_cut, int n_cut,
+                                     const float* g_phi, float* g_vec, float* g_diff, void* stream);
+int gn_embedding_grad_images(const float* g_ctx, const float* feat, int ldf, const float* cut, const int* dst,
+                             const int* colptr, const int* perm, const int* order, const int* sp_ptr, int n_species,
+                             int N, int F, const float* edge_diff, float* work, float* dA_na, float* dA_nbr, void* stream);
 
 /* ---- parameter gradients (first-order training: a loss on energies and / or (h, X)) -------------
  * Every reduction below runs in a fixed order and uses no atomics: identical inputs give identical bits. */
