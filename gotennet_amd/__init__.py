@@ -4,5 +4,6 @@ Public surface mirrors the reference package (gotennet/__init__.py:5-10)."""
 from .engine import attention_dropout_mask  # noqa: F401
 from .gotennet import EQFF, GATA, GotenNet, GotenNetWrapper  # noqa: F401
 from .layers import CosineCutoff  # noqa: F401
+from .md import MDRun  # noqa: F401
 
 __version__ = "0.1.0"

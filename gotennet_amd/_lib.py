@@ -118,6 +118,15 @@ SIGNATURES = {
     "gn_embedding_grad_images": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gn_edge_vectors_pbc": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     "gn_virial": [_P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "gn_radius_verify": [_P, _P, _P, _I, _I, _F, _I, _P, _P, _I, _P, _P, _P, _P],
+    "gn_radius_verify_pbc": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "gn_radius_verify_pbc_images": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "gn_md_kick": [_P, _P, _P, _P, _I, _I, _F, _P, _P],
+    "gn_md_drift": [_P, _P, _I, _F, _P, _P],
+    "gn_md_langevin": [_P, _P, _P, _I, _I, _F, _F, _P, _I, _P, _P],
+    "gn_md_noise": [_P, _L, _I, _I, _P, _P],
+    "gn_md_kinetic": [_P, _P, _P, _I, _P, _I, _I, _F, _P, _P, _P],
+    "gn_md_finish": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "gn_weight_grad_workspace": [_P, _I],
     "gn_weight_grad_group": [_P, _I, _P, _L, _P],
     "gn_weight_grad_workspace_mode": [_P, _I, _I],

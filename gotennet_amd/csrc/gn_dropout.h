@@ -7,9 +7,8 @@
 
 namespace gn {
 
-// Philox4x32-10 (Salmon et al., SC'11; Random123), output word 0 of counter (c0..c3) under key (k0, k1)
-__device__ __forceinline__ unsigned philox4x32_10_word0(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                                        unsigned k0, unsigned k1) {
+// Philox4x32-10 (Salmon et al., SC'11; Random123): the four output words of counter (c0..c3) under key (k0, k1)
+__device__ __forceinline__ uint4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
     constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -22,7 +21,12 @@ __device__ __forceinline__ unsigned philox4x32_10_word0(unsigned c0, unsigned c1
         k0 += W0;
         k1 += W1;
     }
-    return c0;
+    return make_uint4(c0, c1, c2, c3);
+}
+// output word 0 alone (the dropout mask)
+__device__ __forceinline__ unsigned philox4x32_10_word0(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
+                                                        unsigned k0, unsigned k1) {
+    return philox4x32_10(c0, c1, c2, c3, k0, k1).x;
 }
 
 struct AttnDrop {

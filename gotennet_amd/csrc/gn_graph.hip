@@ -360,6 +360,144 @@ __global__ void edge_vectors_pbc_kernel(const float* __restrict__ pos, const int
     edge_diff[e] = is_self_loop(j, i, im) ? 0.0f : sqrtf(im.d2);     // (an atom's own image, shift != 0, is a real edge)
 }
 
+// ================================================================================ is a stored list still the radius graph?
+// gn_radius_verify*: every target walks the candidates of its search in the search's order and asks the search's own
+// predicate (within(), image_of(), shifted()): hit number k must be stored entry k of the target's CSR row (source, and
+// shift for a periodic list), up to the cap, and the number of kept hits must be the row's degree.  Nothing is written but
+// a per-target flag and the sticky word: a row that differs sets state[0] = 1 (plain stores of the same value from every
+// such row; nobody clears it on the device).  Same thread mapping as the searches.
+__device__ __forceinline__ void report_row(bool differs, int i, int* __restrict__ row_flag, int* __restrict__ state) {
+    row_flag[i] = differs ? 1 : 0;
+    if (differs) state[0] = 1;
+}
+// is hit number `slot` of a target something else than entry `slot` of its stored row [e0, e0 + d)?  (shift == nullptr: a
+// list without shifts.  The slot is held to [0, E) all the same: a bad rowptr reads nothing out of bounds.)
+__device__ __forceinline__ bool entry_differs(const int* __restrict__ src, const int* __restrict__ shift, int slot, int d,
+                                              int e0, int E, int j, int sx, int sy, int sz) {
+    const int e = e0 + slot;
+    if (slot >= d || e < 0 || e >= E) return true;
+    if (src[e] != j) return true;
+    return shift != nullptr && (shift[3 * e] != sx || shift[3 * e + 1] != sy || shift[3 * e + 2] != sz);
+}
+
+// one thread per target: radius_count_kernel's loop
+__global__ void radius_verify_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch, int N, float r2,
+                                     int max_nbr, const int* __restrict__ rowptr, const int* __restrict__ src, int E,
+                                     int* __restrict__ row_flag, int* __restrict__ state) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int64_t b = batch[i];
+    const int e0 = rowptr[i], d = rowptr[i + 1] - e0;
+    int c = 0;
+    bool differs = false;
+    for (int j = molecule_start(batch, i); j < N && batch[j] == b && c < max_nbr; ++j) {
+        if (!within(pos, i, j, r2)) continue;
+        differs |= entry_differs(src, nullptr, c, d, e0, E, j, 0, 0, 0);
+        ++c;
+    }
+    report_row(differs || c != d, i, row_flag, state);
+}
+
+// one wave64 per target: radius_pbc_kernel's loop
+__global__ __launch_bounds__(256) void radius_verify_pbc_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch,
+                                                                const int* __restrict__ mol_ptr, const float* __restrict__ cell,
+                                                                const float* __restrict__ inv_cell, int N, int n_mol, float r2,
+                                                                int max_nbr, const int* __restrict__ rowptr,
+                                                                const int* __restrict__ src, const int* __restrict__ shift, int E,
+                                                                int* __restrict__ row_flag, int* __restrict__ state) {
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= N) return;                                // (wave-uniform)
+    const int m = box_of(batch, i, n_mol);
+    const int j0 = mol_ptr[m], j1 = mol_ptr[m + 1];
+    const float* c = cell + 9 * m;
+    const float* ic = inv_cell + 9 * m;
+    const int e0 = rowptr[i], d = rowptr[i + 1] - e0;
+    int cnt = 0;
+    bool differs = false;
+    for (int base = j0; base < j1 && cnt < max_nbr; base += 64) {
+        const int j = base + lane;
+        Image im;
+        bool hit = false;
+        if (j < j1) {
+            im = image_of(pos, i, j, c, ic);
+            hit = im.d2 < r2;
+        }
+        const unsigned long long mask = __ballot(hit);
+        if (hit) {
+            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+            if (slot < max_nbr) differs |= entry_differs(src, shift, slot, d, e0, E, j, im.sx, im.sy, im.sz);
+        }
+        cnt += __popcll(mask);
+    }
+    const bool any = __ballot(differs) != 0ull || (cnt < max_nbr ? cnt : max_nbr) != d;
+    if (lane == 0) report_row(any, i, row_flag, state);
+}
+
+// one wave64 per target: radius_pbc_images_kernel's loop over the flattened (source, image) candidates
+__global__ __launch_bounds__(256) void radius_verify_pbc_images_kernel(
+    const float* __restrict__ pos, const int64_t* __restrict__ batch, const int* __restrict__ mol_ptr,
+    const float* __restrict__ cell, const float* __restrict__ inv_cell, const int* __restrict__ img_range, int N, int n_mol,
+    float r2, int max_nbr, const int* __restrict__ rowptr, const int* __restrict__ src, const int* __restrict__ shift, int E,
+    int* __restrict__ row_flag, int* __restrict__ state) {
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= N) return;                                // (wave-uniform)
+    const int m = box_of(batch, i, n_mol);
+    const int j0 = mol_ptr[m], nj = mol_ptr[m + 1] - j0;
+    const float* c = cell + 9 * m;
+    const float* ic = inv_cell + 9 * m;
+    const int Rx = min(max(img_range[3 * m], 0), GN_PBC_MAX_IMAGE_RANGE);
+    const int Ry = min(max(img_range[3 * m + 1], 0), GN_PBC_MAX_IMAGE_RANGE);
+    const int Rz = min(max(img_range[3 * m + 2], 0), GN_PBC_MAX_IMAGE_RANGE);
+    const int ny = 2 * Ry + 1, nz = 2 * Rz + 1, nyz = ny * nz, n_img = (2 * Rx + 1) * nyz;
+    const float pix = pos[3 * i], piy = pos[3 * i + 1], piz = pos[3 * i + 2];
+    const int e0 = rowptr[i], d = rowptr[i + 1] - e0;
+    int cnt = 0, jb = 0, tb = 0;
+    bool differs = false;
+    while (jb < nj && cnt < max_nbr) {
+        int t = tb + lane;
+        const int dj = t / n_img;
+        t -= dj * n_img;
+        const int j = j0 + jb + dj;
+        Image im;
+        bool hit = false;
+        if (jb + dj < nj) {
+            const int tx = t / nyz, r = t - tx * nyz, ty = r / nz, tz = r - ty * nz;
+            const float dx = pos[3 * j] - pix, dy = pos[3 * j + 1] - piy, dz = pos[3 * j + 2] - piz;
+            const int nx_ = (int)rintf(fmaf(dz, ic[6], fmaf(dy, ic[3], dx * ic[0])));
+            const int ny_ = (int)rintf(fmaf(dz, ic[7], fmaf(dy, ic[4], dx * ic[1])));
+            const int nz_ = (int)rintf(fmaf(dz, ic[8], fmaf(dy, ic[5], dx * ic[2])));
+            im = shifted(dx, dy, dz, tx - Rx - nx_, ty - Ry - ny_, tz - Rz - nz_, c);
+            hit = im.d2 < r2;
+        }
+        const unsigned long long mask = __ballot(hit);
+        if (hit) {
+            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+            if (slot < max_nbr) differs |= entry_differs(src, shift, slot, d, e0, E, j, im.sx, im.sy, im.sz);
+        }
+        cnt += __popcll(mask);
+        tb += 64;
+        jb += tb / n_img;
+        tb %= n_img;
+    }
+    const bool any = __ballot(differs) != 0ull || (cnt < max_nbr ? cnt : max_nbr) != d;
+    if (lane == 0) report_row(any, i, row_flag, state);
+}
+
+// changed[m] = the number of flagged targets of molecule m.  One wave64 per molecule over its atom range, ballot +
+// popcount per trip: an integer count in a fixed order.
+__global__ __launch_bounds__(256) void rows_changed_kernel(const int* __restrict__ row_flag, const int* __restrict__ mol_ptr,
+                                                           int N, int n_mol, int* __restrict__ changed) {
+    const int m = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (m >= n_mol) return;                            // (wave-uniform)
+    const int j0 = max(mol_ptr[m], 0), j1 = min(mol_ptr[m + 1], N);
+    int c = 0;
+    for (int base = j0; base < j1; base += 64) {
+        const int j = base + lane;
+        c += __popcll(__ballot(j < j1 && row_flag[j] != 0));
+    }
+    if (lane == 0) changed[m] = c;
+}
+
 // out[m] = (1 / volume[m]) sum_{e in box m} r_e (x) dE/dr_e,  dE/dr_e = g_vec + g_diff r / |r| (gn_pos_scatter's expression).
 // One workgroup per box over its contiguous edge range; nine sums, wave_sum, then the waves in order through LDS: no
 // atomics, identical inputs give identical bits.  An empty box gives zeros.
@@ -547,4 +685,59 @@ extern "C" int gn_virial(const float* g_vec, const float* g_diff, const float* e
                        g_vec, g_diff, edge_vec, rowptr, mol_ptr, volume, out);
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+
+/* ---- is a stored list still the radius graph of these positions? ----------------------------------------------- */
+static bool radius_verify_args_ok(const float* pos, const int64_t* batch, const int* mol_ptr, int N, int n_mol, int max_nbr,
+                                  const int* rowptr, const int* src, int E, const int* row_flag, const int* changed,
+                                  const int* state) {
+    if (N < 0 || n_mol < 0 || max_nbr <= 0 || E < 0 || !state || (n_mol > 0 && (!changed || !mol_ptr))) return false;
+    return N == 0 || (n_mol >= 1 && pos && batch && rowptr && row_flag && (E == 0 || src));
+}
+static int rows_changed(const int* row_flag, const int* mol_ptr, int N, int n_mol, int* changed, hipStream_t st) {
+    if (n_mol > 0)
+        hipLaunchKernelGGL(gn::rows_changed_kernel, dim3((n_mol + 3) / 4), dim3(256), 0, st, row_flag, mol_ptr, N, n_mol, changed);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_radius_verify(const float* pos, const int64_t* batch, const int* mol_ptr, int N, int n_mol, float cutoff,
+                                int max_nbr, const int* rowptr, const int* src, int E, int* row_flag, int* changed,
+                                int* state, void* stream) {
+    if (!radius_verify_args_ok(pos, batch, mol_ptr, N, n_mol, max_nbr, rowptr, src, E, row_flag, changed, state))
+        return GN_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (N > 0)
+        hipLaunchKernelGGL(gn::radius_verify_kernel, dim3((N + 127) / 128), dim3(128), 0, st, pos, batch, N, cutoff * cutoff,
+                           max_nbr, rowptr, src, E, row_flag, state);
+    return rows_changed(row_flag, mol_ptr, N, n_mol, changed, st);
+}
+
+extern "C" int gn_radius_verify_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                    const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, const int* rowptr,
+                                    const int* src, const int* shift, int E, int* row_flag, int* changed, int* state,
+                                    void* stream) {
+    if (!radius_verify_args_ok(pos, batch, mol_ptr, N, n_mol, max_nbr, rowptr, src, E, row_flag, changed, state) ||
+        (N > 0 && (!cell || !inv_cell)) || (E > 0 && !shift))
+        return GN_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (N > 0)
+        hipLaunchKernelGGL(gn::radius_verify_pbc_kernel, dim3((N + 3) / 4), dim3(256), 0, st, pos, batch, mol_ptr, cell,
+                           inv_cell, N, n_mol, cutoff * cutoff, max_nbr, rowptr, src, shift, E, row_flag, state);
+    return rows_changed(row_flag, mol_ptr, N, n_mol, changed, st);
+}
+
+extern "C" int gn_radius_verify_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                           const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff,
+                                           int max_nbr, const int* rowptr, const int* src, const int* shift, int E,
+                                           int* row_flag, int* changed, int* state, void* stream) {
+    if (!radius_verify_args_ok(pos, batch, mol_ptr, N, n_mol, max_nbr, rowptr, src, E, row_flag, changed, state) ||
+        (N > 0 && (!cell || !inv_cell || !img_range)) || (E > 0 && !shift))
+        return GN_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (N > 0)
+        hipLaunchKernelGGL(gn::radius_verify_pbc_images_kernel, dim3((N + 3) / 4), dim3(256), 0, st, pos, batch, mol_ptr,
+                           cell, inv_cell, img_range, N, n_mol, cutoff * cutoff, max_nbr, rowptr, src, shift, E, row_flag,
+                           state);
+    return rows_changed(row_flag, mol_ptr, N, n_mol, changed, st);
 }

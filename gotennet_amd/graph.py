@@ -206,6 +206,65 @@ def distance_pbc(pos: torch.Tensor, batch: torch.Tensor, cell: torch.Tensor, cut
     return edge_index, edge_diff, edge_vec, edge_shift
 
 
+def verify_list(pos, batch, mol_ptr, n_mol: int, rowptr, src, cutoff: float, max_num_neighbors: int, row_flag, changed, state,
+                shift=None, cell=None, inv_cell=None, image_range=None) -> None:
+    """gn_radius_verify* on prepared device arrays, no allocation and no host read (what a recorded MD step launches): the
+    stored list in CSR form (``rowptr`` int32 [N + 1], ``src`` int32 [E], ``shift`` int32 [E, 3] for a periodic list) against the
+    radius graph of ``pos``.  Writes ``row_flag`` [N], ``changed`` [n_mol] and sets the sticky ``state[0]`` when a row differs.
+    ``cell`` None: the open search; ``image_range`` None: the minimum-image search; else the multi-image one."""
+    N, E = pos.shape[0], src.shape[0]
+    st = torch.cuda.current_stream().cuda_stream
+    tail = (ptr(row_flag), ptr(changed), ptr(state), st)
+    if cell is None:
+        call("gn_radius_verify", ptr(pos), ptr(batch), ptr(mol_ptr), N, n_mol, float(cutoff), int(max_num_neighbors),
+             ptr(rowptr), ptr(src), E, *tail)
+        return
+    box = (ptr(cell), ptr(inv_cell)) if image_range is None else (ptr(cell), ptr(inv_cell), ptr(image_range))
+    call("gn_radius_verify_pbc" + ("" if image_range is None else "_images"), ptr(pos), ptr(batch), ptr(mol_ptr), *box, N, n_mol,
+         float(cutoff), int(max_num_neighbors), ptr(rowptr), ptr(src), ptr(shift), E, *tail)
+
+
+def list_is_current(pos: torch.Tensor, batch: torch.Tensor, edge_index: torch.Tensor, cutoff: float,
+                    max_num_neighbors: int = 32, cell: Optional[torch.Tensor] = None,
+                    edge_shift: Optional[torch.Tensor] = None, images: str = "minimum", n_mol: Optional[int] = None,
+                    state: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Is ``edge_index`` (and ``edge_shift``) still what ``distance`` / ``distance_pbc`` would return for ``pos``?  ->
+    ``changed`` int32 [n_mol]: the number of targets of each molecule whose row of the list differs (all zero: the list is
+    current, to the bit at the threshold -- the check runs the searches' own predicates in their own order, cap included).
+    No list is built and nothing is read back: the result stays on the device.
+
+    ``edge_index`` must be target-major, as the searches return it.  ``cell`` / ``edge_shift`` / ``images`` as for
+    ``distance_pbc`` (the cell is checked the same way, one host read).  ``n_mol``: default from ``cell`` or the last entry of
+    ``batch`` (a host read).  ``state``: an int32 tensor whose first word is set to 1 when any row differs and is never
+    cleared here (the sticky word the MD integrator kernels are predicated on).  ``out``: an int32 [n_mol] result buffer."""
+    if not pos.is_cuda:
+        raise GotenNetHipError("gotennet_amd.graph.list_is_current runs on a ROCm device only (no CPU fallback)")
+    if (cell is None) != (edge_shift is None):
+        raise ValueError("list_is_current: a periodic list needs both cell and edge_shift; neither for isolated molecules")
+    ranges = resolve_images(cell, cutoff, images) if cell is not None else None
+    from .outputs import molecule_ptr
+    dev = pos.device
+    pos = pos.detach().to(torch.float32).contiguous()
+    batch = batch.to(torch.int64).contiguous()
+    N, E = pos.shape[0], edge_index.shape[1]
+    if n_mol is None:
+        n_mol = cell.shape[0] if cell is not None and cell.dim() == 3 else (int(batch[-1].item()) + 1 if N else 0)
+    i32 = dict(dtype=torch.int32, device=dev)
+    src, dst, rowptr = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(N + 1, **i32)
+    st = torch.cuda.current_stream().cuda_stream
+    call("gn_build_csr", ptr(edge_index.contiguous()), E, N, ptr(src), ptr(dst), ptr(rowptr), st)
+    changed = torch.empty(n_mol, **i32) if out is None else out
+    state = torch.zeros(1, **i32) if state is None else state
+    kw = {}
+    if cell is not None:
+        cell = broadcast_cell(cell.to(dev), n_mol)
+        kw = dict(shift=edge_shift.to(torch.int32).contiguous(), cell=cell, inv_cell=cell_prepare(cell)[0],
+                  image_range=None if ranges is None else ranges.expand(n_mol, 3).contiguous().to(dev))
+    verify_list(pos, batch, molecule_ptr(batch, n_mol), n_mol, rowptr, src, cutoff, max_num_neighbors,
+                torch.empty(N, **i32), changed, state, **kw)
+    return changed
+
+
 class PaddedLayout:
     """Fixed sizes for a radius graph that is rebuilt on the device -- an MD step recorded into one hipGraph whose neighbour
     list changes (host work, once per trajectory: the molecule sizes are read here).  The layout only; the kernels that

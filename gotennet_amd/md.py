@@ -1,0 +1,337 @@
+"""Molecular dynamics on the fused energy + force step: velocity Verlet, an optional Langevin thermostat, and a neighbour
+list that is CHECKED on the device inside every replayed step (kernels: csrc/gn_md.hip, gn_radius_verify* in csrc/gn_graph.hip).
+
+One step, in both modes of ``MDRun``::
+
+    kick (previous forces) -> [Langevin half] -> drift -> [Langevin half] -> neighbour list -> model -> kick -> kinetic -> finish
+
+``captured=True`` records that chain around ``CapturedStep``'s body into ONE hipGraph on a fixed edge list, with "neighbour
+list" = gn_radius_verify*: the search's own predicates, in the search's order, compared with the stored rows.  A row that
+differs sets a sticky device word; every integrator kernel is predicated on that word, so a replay on a stale list
+advances nothing.  The host reads the word every ``check_every`` steps; when it is set it rebuilds the list at the frozen
+positions, records a new graph, finishes the interrupted step eagerly with the same kernels, clears the word and goes on.
+``captured=False`` is the same kernel sequence launched eagerly with the list rebuilt by ``graph.distance*`` in every step: the
+reference of the captured mode -- the two trajectories agree bit for bit -- and the better choice for systems whose list
+changes in almost every step.
+
+The cell is fixed for a run: there is no barostat here.
+"""
+from __future__ import annotations
+
+import math
+import weakref
+from typing import Optional
+
+import torch
+
+from . import engine, graph
+from ._lib import call, ptr
+from .outputs import _ATOMIC_MASS, molecule_ptr
+from .pipeline import CapturedStep, EnergyForces
+
+#: ``force_scale`` turns force / mass into an acceleration in the caller's length and time units:
+#: a = force_scale * F / m.  1 when the units are consistent already (the default).  Two common sets, masses in amu,
+#: lengths in Angstrom, times in fs:  forces in eV / Angstrom: 1 eV / (amu Angstrom^2) = 9.648533212e-3 fs^-2 (the Faraday
+#: constant, 96485.33212 C / mol, times 1e-7);  forces in kcal / (mol Angstrom): 4184 J / mol over 1e-3 kg / mol =
+#: 4.184e6 m^2 / s^2 = 4.184e-4 Angstrom^2 / fs^2.  The thermostat's ``kT`` is in the model's energy unit.
+EV_ANGSTROM_AMU_FS = 9.648533212e-3
+KCAL_MOL_ANGSTROM_AMU_FS = 4.184e-4
+
+
+def default_masses() -> torch.Tensor:
+    """The built-in table of standard atomic weights by atomic number (Z <= 36; index 0 is the dummy element, weight 1): the
+    one ``ElectronicSpatialExtentV2`` uses."""
+    return torch.tensor(_ATOMIC_MASS, dtype=torch.float32)
+
+
+def langevin_coefficients(kT: float, gamma: float, h: float, force_scale: float = 1.0):
+    """(c1, c2) of the O step v = c1 v + c2 xi / sqrt(m) over a time h, in fp64: c1 = exp(-gamma h),
+    c2 = sqrt(kT force_scale (1 - c1^2))."""
+    c1 = math.exp(-float(gamma) * float(h))
+    return c1, math.sqrt(float(kT) * float(force_scale) * (1.0 - c1 * c1))
+
+
+def validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images="minimum", check_every=1, log_len=1):
+    """Everything ``MDRun`` refuses, before any launch -> (mass table fp32 on the CPU, ``graph.resolve_images``' result or None).
+    Raises ``ValueError``.  Reads ``z`` (and ``cell``) on the host."""
+    if not (math.isfinite(float(dt)) and float(dt) > 0):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if not (math.isfinite(float(force_scale)) and float(force_scale) > 0):
+        raise ValueError(f"force_scale must be positive and finite, got {force_scale}")
+    if int(check_every) < 1 or int(log_len) < 0:
+        raise ValueError("check_every must be >= 1 and log_len >= 0")
+    table = default_masses() if masses is None else torch.as_tensor(masses).detach().cpu().to(torch.float32).flatten()
+    if table.numel() == 0 or not bool(torch.isfinite(table).all()) or bool((table < 0).any()):
+        raise ValueError("masses: a table of finite, positive masses indexed by atomic number is expected (0 marks an "
+                         "element without a mass)")
+    zc = z.detach().cpu().long()
+    if zc.numel() and (int(zc.min()) < 0 or int(zc.max()) >= table.numel() or bool((table[zc] <= 0).any())):
+        raise ValueError(f"an atomic number has no positive mass in the table ({table.numel()} entries; the built-in one "
+                         "covers Z <= 36): pass masses=")
+    if thermostat is not None:
+        missing = {"kT", "gamma", "key"} - set(thermostat)
+        if missing:
+            raise ValueError(f"thermostat needs kT, gamma and key; missing {sorted(missing)}")
+        kT, gamma = float(thermostat["kT"]), float(thermostat["gamma"])
+        if not (math.isfinite(kT) and math.isfinite(gamma)) or kT < 0 or gamma < 0:
+            raise ValueError(f"thermostat: kT and gamma must be finite and >= 0, got kT={kT}, gamma={gamma}")
+    if pos.requires_grad:
+        raise ValueError("pos requires grad: the driver integrates plain tensors")
+    if cell is not None and cell.requires_grad:
+        raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
+    if images not in graph.IMAGE_MODES:
+        raise ValueError(f"images must be one of {graph.IMAGE_MODES}, got {images!r}")
+    ranges = graph.resolve_images(cell, float(cutoff), images) if cell is not None else None
+    return table, ranges
+
+
+def _key_words(key) -> list:
+    """The thermostat's key as two signed int64 words (an int: {key, 0}; a pair: both)."""
+    words = list(key) if isinstance(key, (tuple, list)) else [key, 0]
+    if len(words) != 2:
+        raise ValueError("thermostat key: an int or a pair of ints")
+    words = [int(w) & (2 ** 64 - 1) for w in words]
+    return [w - 2 ** 64 if w >= 2 ** 63 else w for w in words]
+
+
+class _RecordedStep(CapturedStep):
+    """``CapturedStep`` with the integrator recorded around its body.  The body is run for warm-up while it is recorded: the
+    driver holds the sticky word set during construction, which makes every integrator kernel a no-op.
+
+    The driver is held weakly: driver -> step -> driver would be a reference cycle, and a recorded hipGraph that only the
+    cyclic garbage collector frees may be destroyed in the middle of a later stream capture, which the runtime refuses.  This
+    way the step dies with its driver, or when the driver drops it."""
+
+    def __init__(self, md: "MDRun", edge_index: torch.Tensor, edge_shift: Optional[torch.Tensor]):
+        self.md = weakref.proxy(md)
+        super().__init__(md.ef, md._z, edge_index, md._batch, md.n_mol, cell=md._cell, edge_shift=edge_shift,
+                         check_cell=False, images=md.images)
+
+    def model(self):
+        """The step ``CapturedStep`` records, eagerly: (energy, forces[, stress]) of ``self.pos`` on the stored list."""
+        return super()._body()
+
+    def _body(self):
+        self.md._pre(self.pos)
+        self.md._verify(self.pos, self.g)
+        out = super()._body()
+        self.md._post(*out)
+        return out
+
+
+class _EagerStep:
+    """What ``CapturedStep._body`` reads, for a list that is rebuilt in every step: the same body, launched eagerly."""
+    _body = CapturedStep._body
+
+    def __init__(self, md: "MDRun"):
+        rep = md.ef.rep
+        self.cfg, self.pw, self.head = rep.config(), rep.packed_weights(), md.ef.head
+        self.z32, self.mol_ptr, self.N, self.n_mol, self.pos = md._z32, md._mol_ptr, md.N, md.n_mol, md._pos
+        self.cell, self.batch, self.g = md._cell, md._batch, None
+        if self.cell is not None:
+            self.inv_cell, self.volume = torch.empty_like(self.cell), torch.empty(md.n_mol, dtype=torch.float32, device=self.cell.device)
+
+    def set_list(self, edge_index, edge_shift):
+        self.g = engine.Graph(self.cfg, self.pw, self.N, edge_index.contiguous(), self_images=self.cell is not None)
+        if self.cell is not None:
+            self.g.set_periodic(edge_shift, self.batch, self.cell)
+        self.g.csc()
+
+
+class MDRun:
+    """A trajectory of ``ef``'s model (``pipeline.EnergyForces``) from ``pos`` (and ``vel``, default zero) with time step ``dt``.
+
+        md = MDRun(EnergyForces(rep, head, check_edges=False), z, pos, batch, n_mol, dt=0.5, force_scale=EV_ANGSTROM_AMU_FS,
+                   thermostat=dict(kT=0.0259, gamma=0.01, key=1234))
+        md.run(1000)
+        md.pos, md.vel, md.potential_energy, md.kinetic_energy, md.energy_log(), md.rebuilds
+
+    ``masses``: a table indexed by atomic number (default ``default_masses()``).  ``force_scale``: a = force_scale * F / m in
+    the caller's units (``EV_ANGSTROM_AMU_FS``, ``KCAL_MOL_ANGSTROM_AMU_FS``; default 1: consistent units).  ``cell`` / ``images`` /
+    ``max_num_neighbors``: as ``graph.distance_pbc``; the cell is fixed for the run (no barostat).  ``thermostat``: None (NVE) or
+    ``dict(kT=, gamma=, key=)``: a Langevin O step of half a time step on either side of the drift, its noise a pure function
+    of (key, step, half, atom, component) -- ``gn_md_noise`` reproduces it.  ``check_every``: replays between two host reads of
+    the stale-list word (the trajectory does not depend on it).  ``log_len``: rows of the (potential, kinetic) energy ring
+    buffer.  ``captured=False``: the eager reference (module docstring).
+
+    Refused with ``ValueError`` before any launch: dt <= 0, a negative or missing mass, kT < 0, gamma < 0, a cell that
+    ``graph.resolve_images`` refuses, ``pos`` or ``cell`` requiring grad."""
+
+    def __init__(self, ef: EnergyForces, z: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, n_mol: int, dt: float,
+                 masses=None, force_scale: float = 1.0, vel: Optional[torch.Tensor] = None,
+                 cell: Optional[torch.Tensor] = None, images: str = "minimum", max_num_neighbors: int = 32,
+                 thermostat: Optional[dict] = None, check_every: int = 1, log_len: int = 1024, captured: bool = True):
+        cutoff = float(ef.rep.cutoff)
+        table, ranges = validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images, check_every, log_len)
+        dev = pos.device
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        self.ef, self.n_mol, self.N, self.images = ef, int(n_mol), pos.shape[0], images
+        self.cutoff, self.max_num_neighbors = cutoff, int(max_num_neighbors)
+        self.dt, self.force_scale, self.captured = float(dt), float(force_scale), bool(captured)
+        self.check_every, self.log_len = int(check_every), int(log_len)
+        self._z, self._z32 = z, z.to(torch.int32).contiguous()
+        self._batch = batch.to(torch.int64).contiguous()
+        self._mol_ptr = molecule_ptr(self._batch, self.n_mol)
+        self._mass = table.to(dev)
+        self._cell = self._inv_cell = self._ranges = None
+        if cell is not None:
+            self._cell = graph.broadcast_cell(cell.to(dev), self.n_mol)
+            self._inv_cell = graph.cell_prepare(self._cell)[0]
+            self._ranges = None if ranges is None else ranges.expand(self.n_mol, 3).contiguous().to(dev)
+        self._thermo = None
+        if thermostat is not None:
+            c1, c2 = langevin_coefficients(thermostat["kT"], thermostat["gamma"], 0.5 * self.dt, self.force_scale)
+            self._thermo = (c1, c2, torch.tensor(_key_words(thermostat["key"]), dtype=torch.int64, device=dev))
+        self._vel = torch.zeros((self.N, 3), **f32) if vel is None else vel.detach().to(**f32).clone().contiguous()
+        self._state = torch.zeros(2, **i32)                       # {stale list (sticky), completed steps}
+        self._f = torch.empty((self.N, 3), **f32)                 # forces of the last completed step: the next kick's
+        self._e, self._ke = torch.empty(self.n_mol, **f32), torch.empty(self.n_mol, **f32)
+        self._stress = torch.empty((self.n_mol, 3, 3), **f32) if cell is not None else None
+        self._log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
+        self._row_flag, self._changed = torch.zeros(self.N, **i32), torch.zeros(self.n_mol, **i32)
+        self._done, self.rebuilds, self._fresh = 0, 0, False
+        start = pos.detach().to(**f32).contiguous()
+        lst = self._list(start)
+        if self.captured:
+            self._step, self._pos = None, start
+            self._record(lst)
+            self._state[:1].zero_()
+            with torch.no_grad():
+                out = self._step.model()
+        else:
+            self._pos = start.clone()
+            self._eager, self._lst = _EagerStep(self), lst
+            self._eager.set_list(*lst)
+            with torch.no_grad():
+                out = self._eager._body()
+        self._f.copy_(out[1])
+        self._e.copy_(out[0].reshape(-1))
+        if self._stress is not None:
+            self._stress.copy_(out[2])
+        self._kinetic()
+
+    # ---- the pieces of a step: the same launches whether recorded or eager -----------------------------------------
+    def _list(self, pos):
+        """(edge_index, edge_shift or None) of ``pos``: the project's own search (one host read of the edge count)."""
+        if self._cell is None:
+            return graph.distance(pos, self._batch, self.cutoff, self.max_num_neighbors)[0], None
+        ei, _, _, sh = graph.distance_pbc(pos, self._batch, self._cell, self.cutoff, self.max_num_neighbors, n_mol=self.n_mol,
+                                          check=False, image_range=self._ranges)
+        return ei, sh
+
+    def _kick(self, force):
+        call("gn_md_kick", ptr(self._vel), ptr(force), ptr(self._z32), ptr(self._mass), self._mass.numel(), self.N,
+             float(0.5 * self.dt * self.force_scale), ptr(self._state), engine._stream())
+
+    def _langevin(self, draw):
+        if self._thermo is not None:
+            c1, c2, key = self._thermo
+            call("gn_md_langevin", ptr(self._vel), ptr(self._z32), ptr(self._mass), self._mass.numel(), self.N, float(c1),
+                 float(c2), ptr(key), draw, ptr(self._state), engine._stream())
+
+    def _kinetic(self):
+        call("gn_md_kinetic", ptr(self._vel), ptr(self._z32), ptr(self._mass), self._mass.numel(), ptr(self._mol_ptr), self.N,
+             self.n_mol, float(self.force_scale), ptr(self._ke), ptr(self._state), engine._stream())
+
+    def _pre(self, pos):
+        self._kick(self._f)
+        self._langevin(0)
+        call("gn_md_drift", ptr(pos), ptr(self._vel), self.N, float(self.dt), ptr(self._state), engine._stream())
+        self._langevin(1)
+
+    def _verify(self, pos, g):
+        graph.verify_list(pos, self._batch, self._mol_ptr, self.n_mol, g.rowptr, g.src, self.cutoff, self.max_num_neighbors,
+                          self._row_flag, self._changed, self._state, shift=g.shift, cell=self._cell,
+                          inv_cell=self._inv_cell, image_range=self._ranges)
+
+    def _post(self, energy, forces, stress=None):
+        self._kick(forces)
+        self._kinetic()
+        call("gn_md_finish", ptr(self._state), ptr(forces), ptr(self._f), self.N, ptr(energy), ptr(self._ke), ptr(self._e),
+             ptr(stress), ptr(self._stress), ptr(self._log), self.log_len, self.n_mol, engine._stream())
+
+    # ---- captured mode ---------------------------------------------------------------------------------------------
+    def _record(self, lst):
+        """Record the step on the list ``lst`` and move the positions into its static buffer.  The sticky word is held at 1
+        meanwhile (the recording's warm-up runs advance nothing) and LEFT at 1: the caller clears it."""
+        self._state[:1].fill_(1)
+        pos = self._pos
+        self._step = _RecordedStep(self, lst[0], lst[1])
+        self._step.pos.copy_(pos)
+        self._pos = self._step.pos
+        self._fresh = True
+
+    def _repair(self):
+        """The sticky word is set: positions and velocities are those after the drift of the first incomplete step.  New
+        list there, new graph (the old one is dropped first: one alive at a time), then the rest of that step eagerly."""
+        lst = self._list(self._pos)
+        torch.cuda.synchronize()
+        self._step = None
+        self._record(lst)
+        self._state[:1].zero_()
+        self._post(*self._step.model())
+        self.rebuilds += 1
+        self._done += 1
+
+    @torch.no_grad()
+    def run(self, n: int) -> "MDRun":
+        """Advance ``n`` steps.  Captured: the host reads the device state after every ``check_every`` replays, after the first
+        replay of a newly recorded graph and at the end (a stream synchronisation each)."""
+        if not self.captured:
+            for _ in range(int(n)):
+                self._pre(self._pos)
+                lst = self._list(self._pos)
+                if not (torch.equal(lst[0], self._lst[0]) and (lst[1] is None or torch.equal(lst[1], self._lst[1]))):
+                    self.rebuilds += 1
+                self._lst = lst
+                self._eager.set_list(*lst)
+                self._post(*self._eager._body())
+            self._done += int(n)
+            return self
+        target = self._done + int(n)
+        while self._done < target:
+            burst = 1 if self._fresh else min(self.check_every, target - self._done)
+            for _ in range(burst):
+                self._step.graph.replay()
+            self._fresh = False
+            stale, self._done = self._state.tolist()             # (the synchronisation)
+            if stale:
+                self._repair()
+        return self
+
+    # ---- state and queries -----------------------------------------------------------------------------------------
+    @property
+    def pos(self) -> torch.Tensor:
+        return self._pos.clone()
+
+    @property
+    def vel(self) -> torch.Tensor:
+        return self._vel.clone()
+
+    @property
+    def step(self) -> int:
+        """Completed steps."""
+        return self._done
+
+    @property
+    def potential_energy(self) -> torch.Tensor:
+        """[n_mol], of the last completed step (of the start before the first)."""
+        return self._e.clone()
+
+    @property
+    def kinetic_energy(self) -> torch.Tensor:
+        """[n_mol]: (1/2) sum m v^2 / force_scale, in the model's energy unit."""
+        return self._ke.clone()
+
+    @property
+    def stress(self) -> torch.Tensor:
+        """[n_mol, 3, 3] of the last completed step (periodic runs: ``EnergyForces``' stress)."""
+        if self._stress is None:
+            raise ValueError("stress: this run has no cell")
+        return self._stress.clone()
+
+    def energy_log(self) -> torch.Tensor:
+        """[k, n_mol, 2]: (potential, kinetic) energy after each of the last k = min(step, log_len) steps, oldest first."""
+        k = min(self._done, self.log_len)
+        rows = [(s % self.log_len) for s in range(self._done - k, self._done)]
+        return self._log[torch.tensor(rows, dtype=torch.long, device=self._log.device)]

@@ -544,6 +544,26 @@ int gn_edge_vectors_pbc(const float* pos, const int* src, const int* dst, const 
  * sums, no atomics: identical inputs give identical bits; an empty box gives zeros. */
 int gn_virial(const float* g_vec, const float* g_diff, const float* edge_vec, const int* rowptr, const int* mol_ptr,
               int n_mol, const float* volume, float* out, void* stream);
+/* Is a stored list still the radius graph of these positions?  One entry per search (gn_radius_count, _pbc, _pbc_images),
+ * with that search's arguments plus the stored list in the engine's CSR form: rowptr int32 [N + 1], src int32 [E] (and
+ * shift int32 [E, 3]) of a target-major list, as gn_build_csr writes them.  Every target walks its search's candidates in
+ * the search's order through the search's own device predicates, so the verdict at the threshold is the rebuilt list's, bit
+ * for bit: hit number k (k < max_nbr; the self-loop counts) must be stored entry k of the row -- source, and shift -- and
+ * the number of kept hits must be the row's degree.  Thread mapping as the searches (a thread / a wave64 per target).
+ * Outputs: row_flag int32 [N] (work: 1 where the row differs), changed int32 [n_mol] = flagged targets per molecule
+ * (mol_ptr [n_mol + 1] of gn_molecule_ptr; a wave per molecule, integer count), and the STICKY word state[0], set to 1 by
+ * plain stores when any row differs and never cleared on the device (the gn_md_* kernels below are predicated on it; the
+ * host clears it).  Stored indices are read inside [0, E) only, whatever rowptr holds. */
+int gn_radius_verify(const float* pos, const int64_t* batch, const int* mol_ptr, int N, int n_mol, float cutoff,
+                     int max_nbr, const int* rowptr, const int* src, int E, int* row_flag, int* changed, int* state,
+                     void* stream);
+int gn_radius_verify_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                         const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, const int* rowptr,
+                         const int* src, const int* shift, int E, int* row_flag, int* changed, int* state, void* stream);
+int gn_radius_verify_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff, int max_nbr,
+                                const int* rowptr, const int* src, const int* shift, int E, int* row_flag, int* changed,
+                                int* state, void* stream);
 /* Edge lists with self-images (the *_images radius graph): the five kernels that single out the self-loop -- the unit-vector
  * normalisation of gn_edge_geometry, the NodeInit sum and its backward, gn_edge_geometry_backward, the neighbour-embedding
  * gradient -- tell it by `src == dst AND edge_diff == 0` instead of `src == dst`.  On a list without self-images the two rules
@@ -564,6 +584,38 @@ int gn_edge_geometry_backward_images(const float* edge_vec, const float* edge_di
 int gn_embedding_grad_images(const float* g_ctx, const float* feat, int ldf, const float* cut, const int* dst,
                              const int* colptr, const int* perm, const int* order, const int* sp_ptr, int n_species,
                              int N, int F, const float* edge_diff, float* work, float* dA_na, float* dA_nbr, void* stream);
+
+/* ---- molecular dynamics: the integrator around a recorded energy + force step (gotennet_amd/md.py) ---------------
+ * state int32 [2]: state[0] the sticky stale-list word of gn_radius_verify*, state[1] the number of completed steps.
+ * Every kernel below reads state[0] first and does NOTHING when it is set (gn_md_kick / _drift / _kinetic accept
+ * state == NULL: never frozen): a replay on a stale list moves no atom, velocity, counter or log row.  mass fp32 [n_mass]
+ * is indexed by the atomic number z int32 [N]; an atom whose z is outside the table or whose mass is not positive is left
+ * alone (the caller refuses such inputs).  No atomics, fixed-order sums: identical inputs give identical bits. */
+/* vel += s * force / mass[z]  (s = dt / 2 * force_scale, rounded once on the host) */
+int gn_md_kick(float* vel, const float* force, const int* z, const float* mass, int n_mass, int N, float s,
+               const int* state, void* stream);
+/* pos += dt * vel */
+int gn_md_drift(float* pos, const float* vel, int N, float dt, const int* state, void* stream);
+/* The noise: xi(key, step, draw, atom, component) is a pure function, independent of the launch geometry.  One
+ * Philox4x32-10 evaluation per (atom, pair) with counter (atom, pair + 2 * draw, step, lo32(key[1])) and key
+ * (lo32(key[0]), hi32(key[0])); u1, u2 = ((word0 >> 8) + 1) * 2^-24, ((word1 >> 8) + 1) * 2^-24, uniform in (0, 1];
+ * Box-Muller r = sqrtf(-2 logf(u1)), t = 2 pi u2: pair 0 gives the components x = r cosf(t), y = r sinf(t), pair 1 gives
+ * z = r cosf(t).  `key` is a DEVICE pointer to two int64 values, `draw` numbers the draws inside one step (the two
+ * Langevin halves of md.MDRun are draws 0 and 1), step is 32 bits wide.
+ * gn_md_langevin: the O step vel = c1 * vel + c2 * sqrtf(1 / mass[z]) * xi with step = state[1]; the host passes
+ * c1 = exp(-gamma h), c2 = sqrt(kT force_scale (1 - c1^2)) computed in fp64.  gn_md_noise: out [N, 3] = xi. */
+int gn_md_langevin(float* vel, const int* z, const float* mass, int n_mass, int N, float c1, float c2,
+                   const long long* key, int draw, const int* state, void* stream);
+int gn_md_noise(const long long* key, long step, int draw, int N, float* out, void* stream);
+/* ke[m] = (1/2) sum_{a in molecule m} mass[z_a] |vel_a|^2 / force_scale: one workgroup per molecule, fixed-order sums. */
+int gn_md_kinetic(const float* vel, const int* z, const float* mass, int n_mass, const int* mol_ptr, int N, int n_mol,
+                  float force_scale, float* ke, const int* state, void* stream);
+/* End of a step (one workgroup): with k = state[1], row k % log_len of log [log_len, n_mol, 2] receives (energy[m], ke[m]),
+ * force [N, 3] / energy [n_mol] / stress [n_mol, 9] (NULL: none) are copied into their *_keep buffers -- what the next
+ * kick reads and what the host reads, whatever a later stale replay leaves in the step's own outputs -- and state[1] = k + 1. */
+int gn_md_finish(int* state, const float* force, float* force_keep, int N, const float* energy, const float* ke,
+                 float* energy_keep, const float* stress, float* stress_keep, float* log, int log_len, int n_mol,
+                 void* stream);
 
 /* ---- parameter gradients (first-order training: a loss on energies and / or (h, X)) -------------
  * Every reduction below runs in a fixed order and uses no atomics: identical inputs give identical bits. */
