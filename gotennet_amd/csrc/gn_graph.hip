@@ -6,20 +6,138 @@
 // Output layout = radius_graph's: target-major, sources ascending, strict d^2 < r^2
 // in fp32 (x,y,z accumulated in that order), at most max_nbr sources per target
 // (the first max_nbr in source order), self-loop included.
+//
+// Three searches (isolated molecules, periodic minimum image, periodic multi-image), each asked three questions (how many
+// neighbours, which, is a stored list still the answer).  A search is a WALK: it enumerates a target's candidates in the
+// list's order, decides which are hits and numbers the hits kept under the cap.  A question is a SINK: a small struct,
+// passed to the kernel by value, that the walk hands every kept hit.  Two walks (one thread per target for the open search,
+// one wave per target for the periodic ones) times three sinks: count, fill and verify of one search run the SAME loop and
+// the SAME predicate, so they cannot disagree about which pair is a hit or where it goes (a count and a fill that disagree
+// write out of bounds; a verify that disagrees with the search at the threshold bit breaks an MD trajectory).
 #include "gn_common.h"
 
 namespace gn {
 
-__device__ __forceinline__ bool within(const float* __restrict__ pos, int i, int j, float r2) {
-    const float dx = pos[3 * i] - pos[3 * j];
-    const float dy = pos[3 * i + 1] - pos[3 * j + 1];
-    const float dz = pos[3 * i + 2] - pos[3 * j + 2];
-    float d = dx * dx;
-    d += dy * dy;
-    d += dz * dz;
-    return d < r2;
+// A candidate of target i: source j under the lattice shift s.  v = pos[j] - pos[i] + s @ cell, d2 = |v|^2.
+struct Image {
+    float vx, vy, vz, d2;
+    int sx, sy, sz;
+};
+// |v|^2 accumulated x, y, z: the order of every hit test and every stored distance in this file
+__device__ __forceinline__ float norm2(float x, float y, float z) {
+    float d = x * x;
+    d += y * y;
+    d += z * z;
+    return d;
+}
+// the candidate of an open search: no cell, shift 0
+__device__ __forceinline__ Image unshifted(float dx, float dy, float dz) {
+    return Image{dx, dy, dz, norm2(dx, dy, dz), 0, 0, 0};
+}
+// v = d + s @ cell and |v|^2: the ONLY place a shifted edge vector is computed (the fixed-list kernel calls it with the
+// stored shift, the periodic walk with the candidate's).  The shift always passes through int, so a recomputed and a
+// stored one give the same bits; fmaf in the order a, b, c.
+__device__ __forceinline__ Image shifted(float dx, float dy, float dz, int sx, int sy, int sz, const float* __restrict__ c) {
+    const float fx = (float)sx, fy = (float)sy, fz = (float)sz;
+    Image im;
+    im.sx = sx; im.sy = sy; im.sz = sz;
+    im.vx = fmaf(fz, c[6], fmaf(fy, c[3], fmaf(fx, c[0], dx)));
+    im.vy = fmaf(fz, c[7], fmaf(fy, c[4], fmaf(fx, c[1], dy)));
+    im.vz = fmaf(fz, c[8], fmaf(fy, c[5], fmaf(fx, c[2], dz)));
+    im.d2 = norm2(im.vx, im.vy, im.vz);
+    return im;
+}
+// The self-loop is the edge with j == i AND shift 0; an atom's own periodic image (j == i, shift != 0: cells narrower than
+// 2 * cutoff) is a real neighbour at distance |s @ cell| > 0.  (Open and minimum-image lists: j == i implies shift 0.)
+__device__ __forceinline__ bool is_self_loop(int j, int i, const Image& im) { return j == i && (im.sx | im.sy | im.sz) == 0; }
+
+// The ONLY place an edge is written: slot e of a list of E edges (the caller has checked e < E).  INDEX = false: the list is
+// already stored (the fixed-list kernels); SHIFTS = false: a list without shifts, or with stored ones.  Compile-time both: the
+// fill's loop carries no test of a pointer.
+template <bool INDEX, bool SHIFTS>
+__device__ __forceinline__ void store_edge(int64_t e, int64_t E, int j, int i, const Image& im, int64_t* __restrict__ edge_index,
+                                           int* __restrict__ edge_shift, float* __restrict__ edge_vec,
+                                           float* __restrict__ edge_diff) {
+    if (INDEX) {
+        edge_index[e] = j;                             // row 0: source
+        edge_index[E + e] = i;                         // row 1: target
+    }
+    if (SHIFTS) {
+        edge_shift[3 * e] = im.sx; edge_shift[3 * e + 1] = im.sy; edge_shift[3 * e + 2] = im.sz;
+    }
+    edge_vec[3 * e] = im.vx; edge_vec[3 * e + 1] = im.vy; edge_vec[3 * e + 2] = im.vz;
+    edge_diff[e] = is_self_loop(j, i, im) ? 0.0f : sqrtf(im.d2);
 }
 
+// ================================================================================ the three sinks
+// What a walk asks of a sink, per thread: begin(i) before the first candidate of target i; hit(i, j, slot, im) for hit number
+// `slot` < max_nbr of the target, in the list's order; flag() = this thread saw something to report; finish(i, kept, any) once
+// per target with kept = min(hits, max_nbr) and any = the OR of flag() over the threads that walked the target.
+
+// deg[i] = the number of neighbours kept
+struct CountSink {
+    int* __restrict__ deg;
+    __device__ __forceinline__ void begin(int) {}
+    __device__ __forceinline__ void hit(int, int, int, const Image&) {}
+    __device__ __forceinline__ bool flag() const { return false; }
+    __device__ __forceinline__ void finish(int i, int kept, bool) const { deg[i] = kept; }
+};
+
+// the list itself: rowptr = exclusive scan of deg (length N + 1), E = rowptr[N].  The slot is checked against E all the same.
+// SHIFTS = false: the open search, whose list has no shift array (decided when the kernel is compiled, not per hit).
+template <bool SHIFTS>
+struct FillSink {
+    const int64_t* __restrict__ rowptr;
+    int64_t E;
+    int64_t* __restrict__ edge_index;
+    int* __restrict__ edge_shift;                      // (unused without SHIFTS)
+    float* __restrict__ edge_vec;
+    float* __restrict__ edge_diff;
+    int64_t e0 = 0;
+    __device__ __forceinline__ void begin(int i) { e0 = rowptr[i]; }
+    __device__ __forceinline__ void hit(int i, int j, int slot, const Image& im) const {
+        const int64_t e = e0 + slot;
+        if (e < E) store_edge<true, SHIFTS>(e, E, j, i, im, edge_index, edge_shift, edge_vec, edge_diff);
+    }
+    __device__ __forceinline__ bool flag() const { return false; }
+    __device__ __forceinline__ void finish(int, int, bool) const {}
+};
+
+// Is a stored list still the radius graph?  Hit number k must be stored entry k of the target's CSR row (source, and shift for
+// a periodic list), up to the cap, and the number of kept hits must be the row's degree.  Nothing is written but a per-target
+// flag and the sticky word: a row that differs sets state[0] = 1 (plain stores of the same value from every such row; nobody
+// clears it on the device).
+__device__ __forceinline__ void report_row(bool differs, int i, int* __restrict__ row_flag, int* __restrict__ state) {
+    row_flag[i] = differs ? 1 : 0;
+    if (differs) state[0] = 1;
+}
+// is hit number `slot` of a target something else than entry `slot` of its stored row [e0, e0 + d)?  (shift == nullptr: a
+// list without shifts.  The slot is held to [0, E) all the same: a bad rowptr reads nothing out of bounds.)
+__device__ __forceinline__ bool entry_differs(const int* __restrict__ src, const int* __restrict__ shift, int slot, int d,
+                                              int e0, int E, int j, int sx, int sy, int sz) {
+    const int e = e0 + slot;
+    if (slot >= d || e < 0 || e >= E) return true;
+    if (src[e] != j) return true;
+    return shift != nullptr && (shift[3 * e] != sx || shift[3 * e + 1] != sy || shift[3 * e + 2] != sz);
+}
+struct VerifySink {
+    const int* __restrict__ rowptr;                    // int32 [N + 1]: the stored list in CSR form
+    const int* __restrict__ src;
+    const int* __restrict__ shift;                     // nullptr: the open search
+    int E;
+    int* __restrict__ row_flag;
+    int* __restrict__ state;
+    int e0 = 0, d = 0;
+    bool differs = false;
+    __device__ __forceinline__ void begin(int i) { e0 = rowptr[i]; d = rowptr[i + 1] - e0; }
+    __device__ __forceinline__ void hit(int, int j, int slot, const Image& im) {
+        differs |= entry_differs(src, shift, slot, d, e0, E, j, im.sx, im.sy, im.sz);
+    }
+    __device__ __forceinline__ bool flag() const { return differs; }
+    __device__ __forceinline__ void finish(int i, int kept, bool any) const { report_row(any || kept != d, i, row_flag, state); }
+};
+
+// ================================================================================ isolated molecules: one thread per target
 __device__ __forceinline__ int molecule_start(const int64_t* __restrict__ batch, int i) {
     const int64_t b = batch[i];
     int s = i;
@@ -27,46 +145,32 @@ __device__ __forceinline__ int molecule_start(const int64_t* __restrict__ batch,
     return s;
 }
 
-__global__ void radius_count_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch, int N,
-                                    float r2, int max_nbr, int* __restrict__ deg) {
+// The open walk (gn_radius_count / _fill / _verify): the target's own molecule, sources ascending, until the cap is reached.
+template <class Sink>
+__global__ void radius_thread_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch, int N, float r2,
+                                     int max_nbr, Sink sink) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const int64_t b = batch[i];
-    int c = 0;
-    for (int j = molecule_start(batch, i); j < N && batch[j] == b && c < max_nbr; ++j) c += within(pos, i, j, r2) ? 1 : 0;
-    deg[i] = c;
-}
-
-// rowptr = exclusive scan of deg (length N+1)
-__global__ void radius_fill_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch, int N,
-                                   float r2, int max_nbr, const int64_t* __restrict__ rowptr, int64_t E,
-                                   int64_t* __restrict__ edge_index, float* __restrict__ edge_vec,
-                                   float* __restrict__ edge_diff) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const int64_t b = batch[i];
-    int64_t e = rowptr[i];
-    int c = 0;
-    for (int j = molecule_start(batch, i); j < N && batch[j] == b && c < max_nbr; ++j) {
-        if (!within(pos, i, j, r2)) continue;
-        edge_index[e] = j;           // row 0: source
-        edge_index[E + e] = i;       // row 1: target
-        const float vx = pos[3 * j] - pos[3 * i], vy = pos[3 * j + 1] - pos[3 * i + 1], vz = pos[3 * j + 2] - pos[3 * i + 2];
-        edge_vec[3 * e] = vx; edge_vec[3 * e + 1] = vy; edge_vec[3 * e + 2] = vz;
-        edge_diff[e] = (j == i) ? 0.0f : sqrtf(vx * vx + vy * vy + vz * vz);
-        ++e; ++c;
+    sink.begin(i);
+    int cnt = 0;
+    for (int j = molecule_start(batch, i); j < N && batch[j] == b && cnt < max_nbr; ++j) {
+        const Image im = unshifted(pos[3 * j] - pos[3 * i], pos[3 * j + 1] - pos[3 * i + 1], pos[3 * j + 2] - pos[3 * i + 2]);
+        if (!(im.d2 < r2)) continue;
+        sink.hit(i, j, cnt, im);
+        ++cnt;
     }
+    sink.finish(i, cnt, sink.flag());
 }
 
-// edge vectors of a FIXED edge list for new positions (same arithmetic as radius_fill_kernel)
+// edge vectors of a FIXED edge list for new positions (the open search's arithmetic)
 __global__ void edge_vectors_kernel(const float* __restrict__ pos, const int* __restrict__ src, const int* __restrict__ dst,
                                     int E, float* __restrict__ edge_vec, float* __restrict__ edge_diff) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
     const int j = src[e], i = dst[e];
-    const float vx = pos[3 * j] - pos[3 * i], vy = pos[3 * j + 1] - pos[3 * i + 1], vz = pos[3 * j + 2] - pos[3 * i + 2];
-    edge_vec[3 * e] = vx; edge_vec[3 * e + 1] = vy; edge_vec[3 * e + 2] = vz;
-    edge_diff[e] = (j == i) ? 0.0f : sqrtf(vx * vx + vy * vy + vz * vz);
+    const Image im = unshifted(pos[3 * j] - pos[3 * i], pos[3 * j + 1] - pos[3 * i + 1], pos[3 * j + 2] - pos[3 * i + 2]);
+    store_edge<false, false>(e, E, j, i, im, nullptr, nullptr, edge_vec, edge_diff);
 }
 
 // ---- by-source (CSC) view of a target-major edge list, stable: perm lists the CSR edge ids of every source in increasing
@@ -170,38 +274,6 @@ __global__ void molecule_ptr_kernel(const int64_t* __restrict__ batch, int N, in
 // ================================================================================ periodic boundary conditions
 // Conventions (include/gotennet_hip.h): cell fp32 [n_mol, 3, 3], ROWS are the lattice vectors a, b, c, one cell per entry of
 // `batch` (a "molecule" is a periodic box); edge_shift int32 [E, 3]; edge_vec[e] = pos[j] - pos[i] + edge_shift[e] @ cell.
-// Minimum image (radius_pbc_kernel): the host sends it only cells whose perpendicular widths are at least 2 * cutoff, so
-// each pair has at most one image inside the cutoff and that image has all fractional coordinates in (-1/2, 1/2): rounding
-// the fractional difference finds it, for skewed cells too.  Narrower cells: radius_pbc_images_kernel below.
-struct Image {
-    float vx, vy, vz, d2;
-    int sx, sy, sz;
-};
-// v = d + s @ cell and |v|^2: the ONLY place a shifted edge vector is computed (the fixed-list kernel calls it with the
-// stored shift, count and fill through image_of below).  The shift always passes through int, so a recomputed and a
-// stored one give the same bits; fmaf in the order a, b, c; d^2 accumulated x, y, z as in within().
-__device__ __forceinline__ Image shifted(float dx, float dy, float dz, int sx, int sy, int sz, const float* __restrict__ c) {
-    const float fx = (float)sx, fy = (float)sy, fz = (float)sz;
-    Image im;
-    im.sx = sx; im.sy = sy; im.sz = sz;
-    im.vx = fmaf(fz, c[6], fmaf(fy, c[3], fmaf(fx, c[0], dx)));
-    im.vy = fmaf(fz, c[7], fmaf(fy, c[4], fmaf(fx, c[1], dy)));
-    im.vz = fmaf(fz, c[8], fmaf(fy, c[5], fmaf(fx, c[2], dz)));
-    float d = im.vx * im.vx;
-    d += im.vy * im.vy;
-    d += im.vz * im.vz;
-    im.d2 = d;
-    return im;
-}
-// the minimum image of the pair (j -> i): d = pos[j] - pos[i], n_k = rint(d . column k of inv_cell), shift = -n
-__device__ __forceinline__ Image image_of(const float* __restrict__ pos, int i, int j, const float* __restrict__ c,
-                                          const float* __restrict__ ic) {
-    const float dx = pos[3 * j] - pos[3 * i], dy = pos[3 * j + 1] - pos[3 * i + 1], dz = pos[3 * j + 2] - pos[3 * i + 2];
-    const int nx = (int)rintf(fmaf(dz, ic[6], fmaf(dy, ic[3], dx * ic[0])));
-    const int ny = (int)rintf(fmaf(dz, ic[7], fmaf(dy, ic[4], dx * ic[1])));
-    const int nz = (int)rintf(fmaf(dz, ic[8], fmaf(dy, ic[5], dx * ic[2])));
-    return shifted(dx, dy, dz, -nx, -ny, -nz, c);
-}
 
 // one thread per box: inverse and |det| of its cell (on the device, so a recorded step follows a changing cell)
 __global__ void cell_prepare_kernel(const float* __restrict__ cell, int n_mol, float* __restrict__ inv_cell,
@@ -228,74 +300,26 @@ __device__ __forceinline__ int box_of(const int64_t* __restrict__ batch, int i, 
     return b < 0 ? 0 : (b >= n_mol ? n_mol - 1 : (int)b);
 }
 
-// One wave64 per target atom.  The lanes stride over the box's atoms, 64 per trip; a ballot plus the popcount of the lower
-// lanes gives each hit its slot in source order, and the wave-uniform running count `c` carries the cap across trips: the
-// first max_nbr sources in source order, deterministic, no atomics.  FILL = false counts (deg), FILL = true writes the list
-// -- ONE body, so the two cannot disagree about which pair is a hit (a count and a fill that disagree write out of bounds;
-// the fill checks its slot against E all the same).
-template <bool FILL>
-__global__ __launch_bounds__(256) void radius_pbc_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch,
-                                                         const int* __restrict__ mol_ptr, const float* __restrict__ cell,
-                                                         const float* __restrict__ inv_cell, int N, int n_mol, float r2,
-                                                         int max_nbr, int* __restrict__ deg,
-                                                         const int64_t* __restrict__ rowptr, int64_t E,
-                                                         int64_t* __restrict__ edge_index, int* __restrict__ edge_shift,
-                                                         float* __restrict__ edge_vec, float* __restrict__ edge_diff) {
-    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= N) return;                                // (wave-uniform)
-    const int m = box_of(batch, i, n_mol);
-    const int j0 = mol_ptr[m], j1 = mol_ptr[m + 1];
-    const float* c = cell + 9 * m;
-    const float* ic = inv_cell + 9 * m;
-    const int64_t e0 = FILL ? rowptr[i] : 0;
-    int cnt = 0;
-    for (int base = j0; base < j1 && cnt < max_nbr; base += 64) {
-        const int j = base + lane;
-        Image im;
-        bool hit = false;
-        if (j < j1) {
-            im = image_of(pos, i, j, c, ic);
-            hit = im.d2 < r2;
-        }
-        const unsigned long long mask = __ballot(hit);
-        if (FILL && hit) {
-            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-            const int64_t e = e0 + slot;
-            if (slot < max_nbr && e < E) {
-                edge_index[e] = j;                     // row 0: source
-                edge_index[E + e] = i;                 // row 1: target
-                edge_shift[3 * e] = im.sx; edge_shift[3 * e + 1] = im.sy; edge_shift[3 * e + 2] = im.sz;
-                edge_vec[3 * e] = im.vx; edge_vec[3 * e + 1] = im.vy; edge_vec[3 * e + 2] = im.vz;
-                edge_diff[e] = (j == i) ? 0.0f : sqrtf(im.d2);
-            }
-        }
-        cnt += __popcll(mask);
-    }
-    if (!FILL && lane == 0) deg[i] = cnt < max_nbr ? cnt : max_nbr;
-}
-
-// ---- several images per pair: cells narrower than 2 * cutoff (down to cutoff / 3).
-// The self-loop of such a list is the edge with j == i AND shift 0; an atom's own periodic image (j == i, shift != 0) is a
-// real neighbour at distance |s @ cell| > 0.
-__device__ __forceinline__ bool is_self_loop(int j, int i, const Image& im) { return j == i && (im.sx | im.sy | im.sz) == 0; }
-
-// One wave64 per target atom, as radius_pbc_kernel, over the candidates (source j, image t) of its box: the flattened index
-// q = (j - j0) * n_img + t_flat, t_flat = (tx * ny + ty) * nz + tz (tx slowest), candidate shift s = -rint(f) + (t - R) with
-// f the fractional difference of image_of (the same expression, so R = 0 IS the minimum-image kernel, bit for bit) and
+// The periodic walk (gn_radius_{count,fill,verify}_pbc and their _images forms): one wave64 per target atom over the
+// candidates (source j, image t) of its box.
+//   Candidates.  The flattened index q = (j - j0) * n_img + t_flat, t_flat = (tx * ny + ty) * nz + tz (tx slowest); candidate
+// shift s = -rint(f) + (t - R), f the fractional difference d @ inv_cell of the pair -- formed HERE and nowhere else -- and
 // R = img_range[box] the host's per-axis bound (gn_radius_count_pbc_images in the header: every image inside the cutoff has
 // |s_k + rint(f_k)| <= R_k).  Ascending q is: sources ascending, then shifts ascending lexicographically in (sx, sy, sz).
-// Ballot + popcount of the lower lanes + the running wave-uniform count place each hit and carry the cap across trips: the
-// first max_nbr hits in that order, no atomics.  (jb, tb) = candidate of lane 0 as (source offset, image index): 32-bit
-// throughout, no product of the box size and n_img is ever formed.  FILL as above: one body for count and fill.
-template <bool FILL>
-__global__ __launch_bounds__(256) void radius_pbc_images_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch,
-                                                                const int* __restrict__ mol_ptr, const float* __restrict__ cell,
-                                                                const float* __restrict__ inv_cell,
-                                                                const int* __restrict__ img_range, int N, int n_mol, float r2,
-                                                                int max_nbr, int* __restrict__ deg,
-                                                                const int64_t* __restrict__ rowptr, int64_t E,
-                                                                int64_t* __restrict__ edge_index, int* __restrict__ edge_shift,
-                                                                float* __restrict__ edge_vec, float* __restrict__ edge_diff) {
+//   IMAGES = false is the minimum-image search: R = 0 at compile time, so n_img = 1, every division below folds away and
+// the candidate of a pair is its rounded image, the one inside the cutoff when the cell is at least 2 * cutoff wide (the
+// host sends no other: that image has all fractional coordinates in (-1/2, 1/2), for skewed cells too).  The multi-image
+// search at R = 0 is therefore the minimum-image search bit for bit: it is the same code.
+//   Placement.  The lanes take 64 consecutive candidates per trip; a ballot plus the popcount of the lower lanes gives each
+// hit its slot in candidate order, and the wave-uniform running count carries the cap across trips: the first max_nbr hits
+// in that order, deterministic, no atomics.  (jb, tb) = candidate of lane 0 as (source offset, image index): 32-bit
+// throughout, no product of the box size and n_img is ever formed.
+template <bool IMAGES, class Sink>
+__global__ __launch_bounds__(256) void radius_wave_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch,
+                                                          const int* __restrict__ mol_ptr, const float* __restrict__ cell,
+                                                          const float* __restrict__ inv_cell,
+                                                          const int* __restrict__ img_range, int N, int n_mol, float r2,
+                                                          int max_nbr, Sink sink) {
     const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= N) return;                                // (wave-uniform)
     const int m = box_of(batch, i, n_mol);
@@ -303,12 +327,12 @@ __global__ __launch_bounds__(256) void radius_pbc_images_kernel(const float* __r
     const float* c = cell + 9 * m;
     const float* ic = inv_cell + 9 * m;
     // (the host refuses R > GN_PBC_MAX_IMAGE_RANGE; clamped all the same: a bad array costs images, never a long loop)
-    const int Rx = min(max(img_range[3 * m], 0), GN_PBC_MAX_IMAGE_RANGE);
-    const int Ry = min(max(img_range[3 * m + 1], 0), GN_PBC_MAX_IMAGE_RANGE);
-    const int Rz = min(max(img_range[3 * m + 2], 0), GN_PBC_MAX_IMAGE_RANGE);
+    const int Rx = IMAGES ? min(max(img_range[3 * m], 0), GN_PBC_MAX_IMAGE_RANGE) : 0;
+    const int Ry = IMAGES ? min(max(img_range[3 * m + 1], 0), GN_PBC_MAX_IMAGE_RANGE) : 0;
+    const int Rz = IMAGES ? min(max(img_range[3 * m + 2], 0), GN_PBC_MAX_IMAGE_RANGE) : 0;
     const int ny = 2 * Ry + 1, nz = 2 * Rz + 1, nyz = ny * nz, n_img = (2 * Rx + 1) * nyz;      // <= 343
     const float pix = pos[3 * i], piy = pos[3 * i + 1], piz = pos[3 * i + 2];
-    const int64_t e0 = FILL ? rowptr[i] : 0;
+    sink.begin(i);
     int cnt = 0, jb = 0, tb = 0;
     while (jb < nj && cnt < max_nbr) {
         int t = tb + lane;                             // < n_img + 64
@@ -320,30 +344,22 @@ __global__ __launch_bounds__(256) void radius_pbc_images_kernel(const float* __r
         if (jb + dj < nj) {
             const int tx = t / nyz, r = t - tx * nyz, ty = r / nz, tz = r - ty * nz;
             const float dx = pos[3 * j] - pix, dy = pos[3 * j + 1] - piy, dz = pos[3 * j + 2] - piz;
-            const int nx_ = (int)rintf(fmaf(dz, ic[6], fmaf(dy, ic[3], dx * ic[0])));
-            const int ny_ = (int)rintf(fmaf(dz, ic[7], fmaf(dy, ic[4], dx * ic[1])));
-            const int nz_ = (int)rintf(fmaf(dz, ic[8], fmaf(dy, ic[5], dx * ic[2])));
-            im = shifted(dx, dy, dz, tx - Rx - nx_, ty - Ry - ny_, tz - Rz - nz_, c);
+            const int fx = (int)rintf(fmaf(dz, ic[6], fmaf(dy, ic[3], dx * ic[0])));
+            const int fy = (int)rintf(fmaf(dz, ic[7], fmaf(dy, ic[4], dx * ic[1])));
+            const int fz = (int)rintf(fmaf(dz, ic[8], fmaf(dy, ic[5], dx * ic[2])));
+            im = shifted(dx, dy, dz, tx - Rx - fx, ty - Ry - fy, tz - Rz - fz, c);
             hit = im.d2 < r2;                          // (the self-loop: 0 < r2)
         }
         const unsigned long long mask = __ballot(hit);
-        if (FILL && hit) {
-            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-            const int64_t e = e0 + slot;
-            if (slot < max_nbr && e < E) {
-                edge_index[e] = j;                     // row 0: source
-                edge_index[E + e] = i;                 // row 1: target
-                edge_shift[3 * e] = im.sx; edge_shift[3 * e + 1] = im.sy; edge_shift[3 * e + 2] = im.sz;
-                edge_vec[3 * e] = im.vx; edge_vec[3 * e + 1] = im.vy; edge_vec[3 * e + 2] = im.vz;
-                edge_diff[e] = is_self_loop(j, i, im) ? 0.0f : sqrtf(im.d2);
-            }
-        }
+        const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+        if (hit && slot < max_nbr) sink.hit(i, j, slot, im);
         cnt += __popcll(mask);
         tb += 64;                                      // the next 64 candidates
         jb += tb / n_img;
         tb %= n_img;
     }
-    if (!FILL && lane == 0) deg[i] = cnt < max_nbr ? cnt : max_nbr;
+    const bool any = __ballot(sink.flag()) != 0ull;
+    if (lane == 0) sink.finish(i, cnt < max_nbr ? cnt : max_nbr, any);
 }
 
 // edge vectors of a FIXED periodic edge list for new positions / a new cell: the stored shift, no image search
@@ -356,133 +372,11 @@ __global__ void edge_vectors_pbc_kernel(const float* __restrict__ pos, const int
     const int j = src[e], i = dst[e];
     const float dx = pos[3 * j] - pos[3 * i], dy = pos[3 * j + 1] - pos[3 * i + 1], dz = pos[3 * j + 2] - pos[3 * i + 2];
     const Image im = shifted(dx, dy, dz, shift[3 * e], shift[3 * e + 1], shift[3 * e + 2], cell + 9 * box_of(batch, i, n_mol));
-    edge_vec[3 * e] = im.vx; edge_vec[3 * e + 1] = im.vy; edge_vec[3 * e + 2] = im.vz;
-    edge_diff[e] = is_self_loop(j, i, im) ? 0.0f : sqrtf(im.d2);     // (an atom's own image, shift != 0, is a real edge)
+    store_edge<false, false>(e, E, j, i, im, nullptr, nullptr, edge_vec, edge_diff);     // (an atom's own image, shift != 0, is a real edge)
 }
 
-// ================================================================================ is a stored list still the radius graph?
-// gn_radius_verify*: every target walks the candidates of its search in the search's order and asks the search's own
-// predicate (within(), image_of(), shifted()): hit number k must be stored entry k of the target's CSR row (source, and
-// shift for a periodic list), up to the cap, and the number of kept hits must be the row's degree.  Nothing is written but
-// a per-target flag and the sticky word: a row that differs sets state[0] = 1 (plain stores of the same value from every
-// such row; nobody clears it on the device).  Same thread mapping as the searches.
-__device__ __forceinline__ void report_row(bool differs, int i, int* __restrict__ row_flag, int* __restrict__ state) {
-    row_flag[i] = differs ? 1 : 0;
-    if (differs) state[0] = 1;
-}
-// is hit number `slot` of a target something else than entry `slot` of its stored row [e0, e0 + d)?  (shift == nullptr: a
-// list without shifts.  The slot is held to [0, E) all the same: a bad rowptr reads nothing out of bounds.)
-__device__ __forceinline__ bool entry_differs(const int* __restrict__ src, const int* __restrict__ shift, int slot, int d,
-                                              int e0, int E, int j, int sx, int sy, int sz) {
-    const int e = e0 + slot;
-    if (slot >= d || e < 0 || e >= E) return true;
-    if (src[e] != j) return true;
-    return shift != nullptr && (shift[3 * e] != sx || shift[3 * e + 1] != sy || shift[3 * e + 2] != sz);
-}
-
-// one thread per target: radius_count_kernel's loop
-__global__ void radius_verify_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch, int N, float r2,
-                                     int max_nbr, const int* __restrict__ rowptr, const int* __restrict__ src, int E,
-                                     int* __restrict__ row_flag, int* __restrict__ state) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const int64_t b = batch[i];
-    const int e0 = rowptr[i], d = rowptr[i + 1] - e0;
-    int c = 0;
-    bool differs = false;
-    for (int j = molecule_start(batch, i); j < N && batch[j] == b && c < max_nbr; ++j) {
-        if (!within(pos, i, j, r2)) continue;
-        differs |= entry_differs(src, nullptr, c, d, e0, E, j, 0, 0, 0);
-        ++c;
-    }
-    report_row(differs || c != d, i, row_flag, state);
-}
-
-// one wave64 per target: radius_pbc_kernel's loop
-__global__ __launch_bounds__(256) void radius_verify_pbc_kernel(const float* __restrict__ pos, const int64_t* __restrict__ batch,
-                                                                const int* __restrict__ mol_ptr, const float* __restrict__ cell,
-                                                                const float* __restrict__ inv_cell, int N, int n_mol, float r2,
-                                                                int max_nbr, const int* __restrict__ rowptr,
-                                                                const int* __restrict__ src, const int* __restrict__ shift, int E,
-                                                                int* __restrict__ row_flag, int* __restrict__ state) {
-    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= N) return;                                // (wave-uniform)
-    const int m = box_of(batch, i, n_mol);
-    const int j0 = mol_ptr[m], j1 = mol_ptr[m + 1];
-    const float* c = cell + 9 * m;
-    const float* ic = inv_cell + 9 * m;
-    const int e0 = rowptr[i], d = rowptr[i + 1] - e0;
-    int cnt = 0;
-    bool differs = false;
-    for (int base = j0; base < j1 && cnt < max_nbr; base += 64) {
-        const int j = base + lane;
-        Image im;
-        bool hit = false;
-        if (j < j1) {
-            im = image_of(pos, i, j, c, ic);
-            hit = im.d2 < r2;
-        }
-        const unsigned long long mask = __ballot(hit);
-        if (hit) {
-            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-            if (slot < max_nbr) differs |= entry_differs(src, shift, slot, d, e0, E, j, im.sx, im.sy, im.sz);
-        }
-        cnt += __popcll(mask);
-    }
-    const bool any = __ballot(differs) != 0ull || (cnt < max_nbr ? cnt : max_nbr) != d;
-    if (lane == 0) report_row(any, i, row_flag, state);
-}
-
-// one wave64 per target: radius_pbc_images_kernel's loop over the flattened (source, image) candidates
-__global__ __launch_bounds__(256) void radius_verify_pbc_images_kernel(
-    const float* __restrict__ pos, const int64_t* __restrict__ batch, const int* __restrict__ mol_ptr,
-    const float* __restrict__ cell, const float* __restrict__ inv_cell, const int* __restrict__ img_range, int N, int n_mol,
-    float r2, int max_nbr, const int* __restrict__ rowptr, const int* __restrict__ src, const int* __restrict__ shift, int E,
-    int* __restrict__ row_flag, int* __restrict__ state) {
-    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= N) return;                                // (wave-uniform)
-    const int m = box_of(batch, i, n_mol);
-    const int j0 = mol_ptr[m], nj = mol_ptr[m + 1] - j0;
-    const float* c = cell + 9 * m;
-    const float* ic = inv_cell + 9 * m;
-    const int Rx = min(max(img_range[3 * m], 0), GN_PBC_MAX_IMAGE_RANGE);
-    const int Ry = min(max(img_range[3 * m + 1], 0), GN_PBC_MAX_IMAGE_RANGE);
-    const int Rz = min(max(img_range[3 * m + 2], 0), GN_PBC_MAX_IMAGE_RANGE);
-    const int ny = 2 * Ry + 1, nz = 2 * Rz + 1, nyz = ny * nz, n_img = (2 * Rx + 1) * nyz;
-    const float pix = pos[3 * i], piy = pos[3 * i + 1], piz = pos[3 * i + 2];
-    const int e0 = rowptr[i], d = rowptr[i + 1] - e0;
-    int cnt = 0, jb = 0, tb = 0;
-    bool differs = false;
-    while (jb < nj && cnt < max_nbr) {
-        int t = tb + lane;
-        const int dj = t / n_img;
-        t -= dj * n_img;
-        const int j = j0 + jb + dj;
-        Image im;
-        bool hit = false;
-        if (jb + dj < nj) {
-            const int tx = t / nyz, r = t - tx * nyz, ty = r / nz, tz = r - ty * nz;
-            const float dx = pos[3 * j] - pix, dy = pos[3 * j + 1] - piy, dz = pos[3 * j + 2] - piz;
-            const int nx_ = (int)rintf(fmaf(dz, ic[6], fmaf(dy, ic[3], dx * ic[0])));
-            const int ny_ = (int)rintf(fmaf(dz, ic[7], fmaf(dy, ic[4], dx * ic[1])));
-            const int nz_ = (int)rintf(fmaf(dz, ic[8], fmaf(dy, ic[5], dx * ic[2])));
-            im = shifted(dx, dy, dz, tx - Rx - nx_, ty - Ry - ny_, tz - Rz - nz_, c);
-            hit = im.d2 < r2;
-        }
-        const unsigned long long mask = __ballot(hit);
-        if (hit) {
-            const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-            if (slot < max_nbr) differs |= entry_differs(src, shift, slot, d, e0, E, j, im.sx, im.sy, im.sz);
-        }
-        cnt += __popcll(mask);
-        tb += 64;
-        jb += tb / n_img;
-        tb %= n_img;
-    }
-    const bool any = __ballot(differs) != 0ull || (cnt < max_nbr ? cnt : max_nbr) != d;
-    if (lane == 0) report_row(any, i, row_flag, state);
-}
-
+// ================================================================================ which molecules hold a changed row?
+// gn_radius_verify*: the verify sink above leaves one flag per target (same thread mapping as the searches).
 // changed[m] = the number of flagged targets of molecule m.  One wave64 per molecule over its atom range, ballot +
 // popcount per trip: an integer count in a fixed order.
 __global__ __launch_bounds__(256) void rows_changed_kernel(const int* __restrict__ row_flag, const int* __restrict__ mol_ptr,
@@ -572,95 +466,12 @@ extern "C" int gn_edge_vectors(const float* pos, const int* src, const int* dst,
     return GN_OK;
 }
 
-extern "C" int gn_radius_count(const float* pos, const int64_t* batch, int N, float cutoff, int max_nbr,
-                               int* deg, void* stream) {
-    if (N < 0 || max_nbr <= 0) return GN_ERR_BAD_ARG;
-    if (N == 0) return GN_OK;
-    hipLaunchKernelGGL(gn::radius_count_kernel, dim3((N + 127) / 128), dim3(128), 0, (hipStream_t)stream,
-                       pos, batch, N, cutoff * cutoff, max_nbr, deg);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-extern "C" int gn_radius_fill(const float* pos, const int64_t* batch, int N, float cutoff, int max_nbr,
-                              const int64_t* rowptr, int64_t E, int64_t* edge_index, float* edge_vec,
-                              float* edge_diff, void* stream) {
-    if (N < 0 || max_nbr <= 0 || E < 0) return GN_ERR_BAD_ARG;
-    if (N == 0) return GN_OK;
-    hipLaunchKernelGGL(gn::radius_fill_kernel, dim3((N + 127) / 128), dim3(128), 0, (hipStream_t)stream,
-                       pos, batch, N, cutoff * cutoff, max_nbr, rowptr, E, edge_index, edge_vec, edge_diff);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
 /* ---- periodic boundary conditions ---------------------------------------------------------------------------- */
 extern "C" int gn_cell_prepare(const float* cell, int n_mol, float* inv_cell, float* volume, void* stream) {
     if (n_mol < 0 || (n_mol > 0 && (!cell || !inv_cell || !volume))) return GN_ERR_BAD_ARG;
     if (n_mol == 0) return GN_OK;
     hipLaunchKernelGGL(gn::cell_prepare_kernel, dim3((n_mol + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        cell, n_mol, inv_cell, volume);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-extern "C" int gn_radius_count_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
-                                   const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, int* deg,
-                                   void* stream) {
-    if (N < 0 || max_nbr <= 0 || n_mol < 0 || (N > 0 && (n_mol < 1 || !pos || !batch || !mol_ptr || !cell || !inv_cell || !deg)))
-        return GN_ERR_BAD_ARG;
-    if (N == 0) return GN_OK;
-    hipLaunchKernelGGL(gn::radius_pbc_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       pos, batch, mol_ptr, cell, inv_cell, N, n_mol, cutoff * cutoff, max_nbr, deg,
-                       (const int64_t*)nullptr, (int64_t)0, (int64_t*)nullptr, (int*)nullptr, (float*)nullptr, (float*)nullptr);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-extern "C" int gn_radius_fill_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
-                                  const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr,
-                                  const int64_t* rowptr, int64_t E, int64_t* edge_index, int* edge_shift,
-                                  float* edge_vec, float* edge_diff, void* stream) {
-    if (N < 0 || max_nbr <= 0 || E < 0 || n_mol < 0 || (N > 0 && (n_mol < 1 || !pos || !batch || !mol_ptr || !cell || !inv_cell || !rowptr)))
-        return GN_ERR_BAD_ARG;
-    if (E > 0 && (!edge_index || !edge_shift || !edge_vec || !edge_diff)) return GN_ERR_BAD_ARG;
-    if (N == 0 || E == 0) return GN_OK;
-    hipLaunchKernelGGL(gn::radius_pbc_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       pos, batch, mol_ptr, cell, inv_cell, N, n_mol, cutoff * cutoff, max_nbr, (int*)nullptr,
-                       rowptr, E, edge_index, edge_shift, edge_vec, edge_diff);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-static bool radius_pbc_args_ok(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
-                               const float* inv_cell, const int* img_range, int N, int n_mol, int max_nbr) {
-    if (N < 0 || max_nbr <= 0 || n_mol < 0) return false;
-    return N == 0 || (n_mol >= 1 && pos && batch && mol_ptr && cell && inv_cell && img_range);
-}
-
-extern "C" int gn_radius_count_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
-                                          const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff,
-                                          int max_nbr, int* deg, void* stream) {
-    if (!radius_pbc_args_ok(pos, batch, mol_ptr, cell, inv_cell, img_range, N, n_mol, max_nbr) || (N > 0 && !deg))
-        return GN_ERR_BAD_ARG;
-    if (N == 0) return GN_OK;
-    hipLaunchKernelGGL(gn::radius_pbc_images_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       pos, batch, mol_ptr, cell, inv_cell, img_range, N, n_mol, cutoff * cutoff, max_nbr, deg,
-                       (const int64_t*)nullptr, (int64_t)0, (int64_t*)nullptr, (int*)nullptr, (float*)nullptr, (float*)nullptr);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-extern "C" int gn_radius_fill_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
-                                         const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff,
-                                         int max_nbr, const int64_t* rowptr, int64_t E, int64_t* edge_index,
-                                         int* edge_shift, float* edge_vec, float* edge_diff, void* stream) {
-    if (!radius_pbc_args_ok(pos, batch, mol_ptr, cell, inv_cell, img_range, N, n_mol, max_nbr) || E < 0 || (N > 0 && !rowptr))
-        return GN_ERR_BAD_ARG;
-    if (E > 0 && (!edge_index || !edge_shift || !edge_vec || !edge_diff)) return GN_ERR_BAD_ARG;
-    if (N == 0 || E == 0) return GN_OK;
-    hipLaunchKernelGGL(gn::radius_pbc_images_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       pos, batch, mol_ptr, cell, inv_cell, img_range, N, n_mol, cutoff * cutoff, max_nbr, (int*)nullptr,
-                       rowptr, E, edge_index, edge_shift, edge_vec, edge_diff);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }
@@ -687,57 +498,150 @@ extern "C" int gn_virial(const float* g_vec, const float* g_diff, const float* e
     return GN_OK;
 }
 
-/* ---- is a stored list still the radius graph of these positions? ----------------------------------------------- */
-static bool radius_verify_args_ok(const float* pos, const int64_t* batch, const int* mol_ptr, int N, int n_mol, int max_nbr,
-                                  const int* rowptr, const int* src, int E, const int* row_flag, const int* changed,
-                                  const int* state) {
-    if (N < 0 || n_mol < 0 || max_nbr <= 0 || E < 0 || !state || (n_mol > 0 && (!changed || !mol_ptr))) return false;
-    return N == 0 || (n_mol >= 1 && pos && batch && rowptr && row_flag && (E == 0 || src));
+/* ---- the radius searches: nine entry points = three searches x three sinks ------------------------------------------ */
+// What an entry point says about its search.  The open entry points take no mol_ptr / n_mol for the search itself (the
+// verify one passes both for the per-molecule counts) and have always taken their pointers on trust.
+struct Search {
+    const float* pos;
+    const int64_t* batch;
+    int N;
+    float cutoff;
+    int max_nbr;
+    bool periodic = false, images = false;
+    const int* mol_ptr = nullptr;
+    int n_mol = 0;
+    const float* cell = nullptr;
+    const float* inv_cell = nullptr;
+    const int* img_range = nullptr;
+};
+static Search periodic_search(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                              const float* inv_cell, const int* img_range, bool images, int N, int n_mol, float cutoff,
+                              int max_nbr) {
+    return Search{pos, batch, N, cutoff, max_nbr, true, images, mol_ptr, n_mol, cell, inv_cell, img_range};
 }
-static int rows_changed(const int* row_flag, const int* mol_ptr, int N, int n_mol, int* changed, hipStream_t st) {
-    if (n_mol > 0)
-        hipLaunchKernelGGL(gn::rows_changed_kernel, dim3((n_mol + 3) / 4), dim3(256), 0, st, row_flag, mol_ptr, N, n_mol, changed);
+static bool search_ok(const Search& s) {
+    if (s.N < 0 || s.max_nbr <= 0) return false;
+    if (!s.periodic) return true;
+    if (s.n_mol < 0) return false;
+    return s.N == 0 || (s.n_mol >= 1 && s.pos && s.batch && s.mol_ptr && s.cell && s.inv_cell && (!s.images || s.img_range));
+}
+// one launch helper per walk: each kernel template is launched from here and nowhere else
+template <class Sink>
+static int launch_thread_walk(const Search& s, const Sink& sink, void* stream) {
+    hipLaunchKernelGGL((gn::radius_thread_kernel<Sink>), dim3((s.N + 127) / 128), dim3(128), 0, (hipStream_t)stream, s.pos, s.batch,
+                       s.N, s.cutoff * s.cutoff, s.max_nbr, sink);
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+template <class Sink>
+static int launch_wave_walk(const Search& s, const Sink& sink, void* stream) {
+    const dim3 grid((s.N + 3) / 4), block(256);
+    const float r2 = s.cutoff * s.cutoff;
+    if (s.images)
+        hipLaunchKernelGGL((gn::radius_wave_kernel<true, Sink>), grid, block, 0, (hipStream_t)stream, s.pos, s.batch, s.mol_ptr,
+                           s.cell, s.inv_cell, s.img_range, s.N, s.n_mol, r2, s.max_nbr, sink);
+    else
+        hipLaunchKernelGGL((gn::radius_wave_kernel<false, Sink>), grid, block, 0, (hipStream_t)stream, s.pos, s.batch, s.mol_ptr,
+                           s.cell, s.inv_cell, s.img_range, s.N, s.n_mol, r2, s.max_nbr, sink);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+template <class Sink>
+static int launch_walk(const Search& s, const Sink& sink, void* stream) {
+    return s.periodic ? launch_wave_walk(s, sink, stream) : launch_thread_walk(s, sink, stream);
+}
+
+static int search_count(const Search& s, int* deg, void* stream) {
+    if (!search_ok(s) || (s.periodic && s.N > 0 && !deg)) return GN_ERR_BAD_ARG;
+    if (s.N == 0) return GN_OK;
+    return launch_walk(s, gn::CountSink{deg}, stream);
+}
+template <bool SHIFTS>
+static int search_fill(const Search& s, const gn::FillSink<SHIFTS>& f, void* stream) {
+    if (!search_ok(s) || f.E < 0) return GN_ERR_BAD_ARG;
+    if (s.periodic && ((s.N > 0 && !f.rowptr) || (f.E > 0 && (!f.edge_index || !f.edge_shift || !f.edge_vec || !f.edge_diff))))
+        return GN_ERR_BAD_ARG;
+    if (s.N == 0 || (s.periodic && f.E == 0)) return GN_OK;
+    if constexpr (SHIFTS) return launch_wave_walk(s, f, stream);           // (a list with shifts is a periodic one)
+    else return launch_thread_walk(s, f, stream);
+}
+// the walk leaves row_flag; then changed[m] = the flagged targets of molecule m
+static int search_verify(const Search& s, const gn::VerifySink& v, int* changed, void* stream) {
+    if (!search_ok(s) || s.n_mol < 0 || v.E < 0 || !v.state || (s.n_mol > 0 && (!changed || !s.mol_ptr))) return GN_ERR_BAD_ARG;
+    if (s.N > 0 && !(s.n_mol >= 1 && s.pos && s.batch && v.rowptr && v.row_flag && (v.E == 0 || v.src))) return GN_ERR_BAD_ARG;
+    if (s.periodic && v.E > 0 && !v.shift) return GN_ERR_BAD_ARG;
+    if (s.N > 0) {
+        const int rc = launch_walk(s, v, stream);
+        if (rc != GN_OK) return rc;
+    }
+    if (s.n_mol > 0)
+        hipLaunchKernelGGL(gn::rows_changed_kernel, dim3((s.n_mol + 3) / 4), dim3(256), 0, (hipStream_t)stream, v.row_flag,
+                           s.mol_ptr, s.N, s.n_mol, changed);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_radius_count(const float* pos, const int64_t* batch, int N, float cutoff, int max_nbr,
+                               int* deg, void* stream) {
+    return search_count(Search{pos, batch, N, cutoff, max_nbr}, deg, stream);
+}
+
+extern "C" int gn_radius_fill(const float* pos, const int64_t* batch, int N, float cutoff, int max_nbr,
+                              const int64_t* rowptr, int64_t E, int64_t* edge_index, float* edge_vec,
+                              float* edge_diff, void* stream) {
+    return search_fill(Search{pos, batch, N, cutoff, max_nbr}, gn::FillSink<false>{rowptr, E, edge_index, nullptr, edge_vec, edge_diff},
+                       stream);
 }
 
 extern "C" int gn_radius_verify(const float* pos, const int64_t* batch, const int* mol_ptr, int N, int n_mol, float cutoff,
                                 int max_nbr, const int* rowptr, const int* src, int E, int* row_flag, int* changed,
                                 int* state, void* stream) {
-    if (!radius_verify_args_ok(pos, batch, mol_ptr, N, n_mol, max_nbr, rowptr, src, E, row_flag, changed, state))
-        return GN_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (N > 0)
-        hipLaunchKernelGGL(gn::radius_verify_kernel, dim3((N + 127) / 128), dim3(128), 0, st, pos, batch, N, cutoff * cutoff,
-                           max_nbr, rowptr, src, E, row_flag, state);
-    return rows_changed(row_flag, mol_ptr, N, n_mol, changed, st);
+    Search s{pos, batch, N, cutoff, max_nbr};
+    s.mol_ptr = mol_ptr;
+    s.n_mol = n_mol;
+    return search_verify(s, gn::VerifySink{rowptr, src, nullptr, E, row_flag, state}, changed, stream);
+}
+
+extern "C" int gn_radius_count_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                   const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, int* deg,
+                                   void* stream) {
+    return search_count(periodic_search(pos, batch, mol_ptr, cell, inv_cell, nullptr, false, N, n_mol, cutoff, max_nbr), deg, stream);
+}
+
+extern "C" int gn_radius_fill_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                  const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr,
+                                  const int64_t* rowptr, int64_t E, int64_t* edge_index, int* edge_shift,
+                                  float* edge_vec, float* edge_diff, void* stream) {
+    return search_fill(periodic_search(pos, batch, mol_ptr, cell, inv_cell, nullptr, false, N, n_mol, cutoff, max_nbr),
+                       gn::FillSink<true>{rowptr, E, edge_index, edge_shift, edge_vec, edge_diff}, stream);
 }
 
 extern "C" int gn_radius_verify_pbc(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
                                     const float* inv_cell, int N, int n_mol, float cutoff, int max_nbr, const int* rowptr,
                                     const int* src, const int* shift, int E, int* row_flag, int* changed, int* state,
                                     void* stream) {
-    if (!radius_verify_args_ok(pos, batch, mol_ptr, N, n_mol, max_nbr, rowptr, src, E, row_flag, changed, state) ||
-        (N > 0 && (!cell || !inv_cell)) || (E > 0 && !shift))
-        return GN_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (N > 0)
-        hipLaunchKernelGGL(gn::radius_verify_pbc_kernel, dim3((N + 3) / 4), dim3(256), 0, st, pos, batch, mol_ptr, cell,
-                           inv_cell, N, n_mol, cutoff * cutoff, max_nbr, rowptr, src, shift, E, row_flag, state);
-    return rows_changed(row_flag, mol_ptr, N, n_mol, changed, st);
+    return search_verify(periodic_search(pos, batch, mol_ptr, cell, inv_cell, nullptr, false, N, n_mol, cutoff, max_nbr),
+                         gn::VerifySink{rowptr, src, shift, E, row_flag, state}, changed, stream);
+}
+
+extern "C" int gn_radius_count_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                          const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff,
+                                          int max_nbr, int* deg, void* stream) {
+    return search_count(periodic_search(pos, batch, mol_ptr, cell, inv_cell, img_range, true, N, n_mol, cutoff, max_nbr), deg, stream);
+}
+
+extern "C" int gn_radius_fill_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
+                                         const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff,
+                                         int max_nbr, const int64_t* rowptr, int64_t E, int64_t* edge_index,
+                                         int* edge_shift, float* edge_vec, float* edge_diff, void* stream) {
+    return search_fill(periodic_search(pos, batch, mol_ptr, cell, inv_cell, img_range, true, N, n_mol, cutoff, max_nbr),
+                       gn::FillSink<true>{rowptr, E, edge_index, edge_shift, edge_vec, edge_diff}, stream);
 }
 
 extern "C" int gn_radius_verify_pbc_images(const float* pos, const int64_t* batch, const int* mol_ptr, const float* cell,
                                            const float* inv_cell, const int* img_range, int N, int n_mol, float cutoff,
                                            int max_nbr, const int* rowptr, const int* src, const int* shift, int E,
                                            int* row_flag, int* changed, int* state, void* stream) {
-    if (!radius_verify_args_ok(pos, batch, mol_ptr, N, n_mol, max_nbr, rowptr, src, E, row_flag, changed, state) ||
-        (N > 0 && (!cell || !inv_cell || !img_range)) || (E > 0 && !shift))
-        return GN_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (N > 0)
-        hipLaunchKernelGGL(gn::radius_verify_pbc_images_kernel, dim3((N + 3) / 4), dim3(256), 0, st, pos, batch, mol_ptr,
-                           cell, inv_cell, img_range, N, n_mol, cutoff * cutoff, max_nbr, rowptr, src, shift, E, row_flag,
-                           state);
-    return rows_changed(row_flag, mol_ptr, N, n_mol, changed, st);
+    return search_verify(periodic_search(pos, batch, mol_ptr, cell, inv_cell, img_range, true, N, n_mol, cutoff, max_nbr),
+                         gn::VerifySink{rowptr, src, shift, E, row_flag, state}, changed, stream);
 }

@@ -24,18 +24,27 @@ def distance(pos: torch.Tensor, batch: torch.Tensor, cutoff: float, max_num_neig
     pos = pos.detach().to(torch.float32).contiguous()
     batch = batch.to(torch.int64).contiguous()
     N = pos.shape[0]
+    search = (ptr(pos), ptr(batch), N, float(cutoff), int(max_num_neighbors))
+    return _count_and_fill("", search, N, pos.device, shifts=False)[:3]
+
+
+def _count_and_fill(entry: str, search: tuple, N: int, device, shifts: bool):
+    """The host sequence of every search, gn_radius_count<entry> / gn_radius_fill<entry>: count, exclusive scan, ONE read of
+    the edge count, allocate, fill -> (edge_index, edge_diff, edge_vec, edge_shift or None).  ``search``: the arguments the
+    two entry points share, up to and including the cap."""
     st = torch.cuda.current_stream().cuda_stream
-    deg = torch.empty(N, dtype=torch.int32, device=pos.device)
-    call("gn_radius_count", ptr(pos), ptr(batch), N, float(cutoff), int(max_num_neighbors), ptr(deg), st)
-    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=pos.device)
+    deg = torch.empty(N, dtype=torch.int32, device=device)
+    call("gn_radius_count" + entry, *search, ptr(deg), st)
+    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=device)
     torch.cumsum(deg, 0, out=rowptr[1:])
     E = int(rowptr[-1].item()) if N else 0
-    edge_index = torch.empty((2, E), dtype=torch.int64, device=pos.device)
-    edge_vec = torch.empty((E, 3), dtype=torch.float32, device=pos.device)
-    edge_diff = torch.empty(E, dtype=torch.float32, device=pos.device)
-    call("gn_radius_fill", ptr(pos), ptr(batch), N, float(cutoff), int(max_num_neighbors), ptr(rowptr), E,
-         ptr(edge_index), ptr(edge_vec), ptr(edge_diff), st)
-    return edge_index, edge_diff, edge_vec
+    edge_index = torch.empty((2, E), dtype=torch.int64, device=device)
+    edge_shift = torch.empty((E, 3), dtype=torch.int32, device=device) if shifts else None
+    edge_vec = torch.empty((E, 3), dtype=torch.float32, device=device)
+    edge_diff = torch.empty(E, dtype=torch.float32, device=device)
+    outs = (ptr(edge_index),) + ((ptr(edge_shift),) if shifts else ()) + (ptr(edge_vec), ptr(edge_diff))
+    call("gn_radius_fill" + entry, *search, ptr(rowptr), E, *outs, st)
+    return edge_index, edge_diff, edge_vec, edge_shift
 
 
 
@@ -125,6 +134,21 @@ def cell_prepare(cell: torch.Tensor, inv_cell: Optional[torch.Tensor] = None, vo
     return inv_cell, volume
 
 
+def default_n_mol(batch: torch.Tensor, cell: Optional[torch.Tensor] = None) -> int:
+    """The number of molecules when the caller names none: one per cell of a [n_mol, 3, 3] ``cell``, else from the last entry
+    of ``batch`` (a host read)."""
+    if cell is not None and cell.dim() == 3:
+        return cell.shape[0]
+    return int(batch[-1].item()) + 1 if batch.shape[0] else 0
+
+
+def box_arrays(cell: torch.Tensor, ranges: Optional[torch.Tensor], n_mol: int, device):
+    """What the periodic kernels read per box, on ``device`` -> (cell fp32 [n_mol, 3, 3], its inverse (gn_cell_prepare), the
+    image range int32 [n_mol, 3] or None).  ``ranges``: ``resolve_images``' result."""
+    cell = broadcast_cell(cell.to(device), n_mol)
+    return cell, cell_prepare(cell)[0], None if ranges is None else ranges.expand(n_mol, 3).contiguous().to(device)
+
+
 IMAGE_MODES = ("minimum", "auto", "all")
 
 
@@ -181,29 +205,12 @@ def distance_pbc(pos: torch.Tensor, batch: torch.Tensor, cell: torch.Tensor, cut
     batch = batch.to(torch.int64).contiguous()
     N = pos.shape[0]
     if n_mol is None:
-        n_mol = cell.shape[0] if cell.dim() == 3 else (int(batch[-1].item()) + 1 if N else 0)
-    cell = broadcast_cell(cell.to(pos.device), n_mol)
-    st = torch.cuda.current_stream().cuda_stream
+        n_mol = default_n_mol(batch, cell)
+    cell, inv_cell, ranges = box_arrays(cell, ranges, n_mol, pos.device)
     mol_ptr = molecule_ptr(batch, n_mol)
-    inv_cell, _ = cell_prepare(cell)
-    if ranges is None:
-        sfx, box = "", (ptr(cell), ptr(inv_cell))
-    else:
-        ranges = ranges.expand(n_mol, 3).contiguous().to(pos.device)
-        sfx, box = "_images", (ptr(cell), ptr(inv_cell), ptr(ranges))
-    deg = torch.empty(N, dtype=torch.int32, device=pos.device)
-    call("gn_radius_count_pbc" + sfx, ptr(pos), ptr(batch), ptr(mol_ptr), *box, N, n_mol, float(cutoff),
-         int(max_num_neighbors), ptr(deg), st)
-    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=pos.device)
-    torch.cumsum(deg, 0, out=rowptr[1:])
-    E = int(rowptr[-1].item()) if N else 0
-    edge_index = torch.empty((2, E), dtype=torch.int64, device=pos.device)
-    edge_shift = torch.empty((E, 3), dtype=torch.int32, device=pos.device)
-    edge_vec = torch.empty((E, 3), dtype=torch.float32, device=pos.device)
-    edge_diff = torch.empty(E, dtype=torch.float32, device=pos.device)
-    call("gn_radius_fill_pbc" + sfx, ptr(pos), ptr(batch), ptr(mol_ptr), *box, N, n_mol, float(cutoff),
-         int(max_num_neighbors), ptr(rowptr), E, ptr(edge_index), ptr(edge_shift), ptr(edge_vec), ptr(edge_diff), st)
-    return edge_index, edge_diff, edge_vec, edge_shift
+    box = (ptr(cell), ptr(inv_cell)) if ranges is None else (ptr(cell), ptr(inv_cell), ptr(ranges))
+    search = (ptr(pos), ptr(batch), ptr(mol_ptr), *box, N, n_mol, float(cutoff), int(max_num_neighbors))
+    return _count_and_fill("_pbc" if ranges is None else "_pbc_images", search, N, pos.device, shifts=True)
 
 
 def verify_list(pos, batch, mol_ptr, n_mol: int, rowptr, src, cutoff: float, max_num_neighbors: int, row_flag, changed, state,
@@ -248,7 +255,7 @@ def list_is_current(pos: torch.Tensor, batch: torch.Tensor, edge_index: torch.Te
     batch = batch.to(torch.int64).contiguous()
     N, E = pos.shape[0], edge_index.shape[1]
     if n_mol is None:
-        n_mol = cell.shape[0] if cell is not None and cell.dim() == 3 else (int(batch[-1].item()) + 1 if N else 0)
+        n_mol = default_n_mol(batch, cell)
     i32 = dict(dtype=torch.int32, device=dev)
     src, dst, rowptr = torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(N + 1, **i32)
     st = torch.cuda.current_stream().cuda_stream
@@ -257,9 +264,8 @@ def list_is_current(pos: torch.Tensor, batch: torch.Tensor, edge_index: torch.Te
     state = torch.zeros(1, **i32) if state is None else state
     kw = {}
     if cell is not None:
-        cell = broadcast_cell(cell.to(dev), n_mol)
-        kw = dict(shift=edge_shift.to(torch.int32).contiguous(), cell=cell, inv_cell=cell_prepare(cell)[0],
-                  image_range=None if ranges is None else ranges.expand(n_mol, 3).contiguous().to(dev))
+        cell, inv_cell, ranges = box_arrays(cell, ranges, n_mol, dev)
+        kw = dict(shift=edge_shift.to(torch.int32).contiguous(), cell=cell, inv_cell=inv_cell, image_range=ranges)
     verify_list(pos, batch, molecule_ptr(batch, n_mol), n_mol, rowptr, src, cutoff, max_num_neighbors,
                 torch.empty(N, **i32), changed, state, **kw)
     return changed

@@ -175,9 +175,7 @@ class MDRun:
         self._mass = table.to(dev)
         self._cell = self._inv_cell = self._ranges = None
         if cell is not None:
-            self._cell = graph.broadcast_cell(cell.to(dev), self.n_mol)
-            self._inv_cell = graph.cell_prepare(self._cell)[0]
-            self._ranges = None if ranges is None else ranges.expand(self.n_mol, 3).contiguous().to(dev)
+            self._cell, self._inv_cell, self._ranges = graph.box_arrays(cell, ranges, self.n_mol, dev)
         self._thermo = None
         if thermostat is not None:
             c1, c2 = langevin_coefficients(thermostat["kT"], thermostat["gamma"], 0.5 * self.dt, self.force_scale)
