@@ -127,6 +127,10 @@ SIGNATURES = {
     "gn_md_noise": [_P, _L, _I, _I, _P, _P],
     "gn_md_kinetic": [_P, _P, _P, _I, _P, _I, _I, _F, _P, _P, _P],
     "gn_md_finish": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "gn_npt_pressure": [_P, _P, _P, _I, _P, _P, _I, _P, _P],
+    "gn_npt_barostat": [_P, _P, _P, _I, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P],
+    "gn_npt_rescale": [_P, _P, _P, _P, _P, _I, _I, _P, _P],
+    "gn_npt_cell_guard": [_P, _I, _D, _P, _P, _P, _P],
     "gn_weight_grad_workspace": [_P, _I],
     "gn_weight_grad_group": [_P, _I, _P, _L, _P],
     "gn_weight_grad_workspace_mode": [_P, _I, _I],

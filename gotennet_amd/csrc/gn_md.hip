@@ -1,6 +1,6 @@
 // gn_md.hip -- the integrator of a molecular-dynamics step recorded around the energy + force step (gotennet_amd/md.py):
-// velocity-Verlet kick and drift, the Langevin O step with its noise drawn on the device, the kinetic energy and the
-// end-of-step bookkeeping.
+// velocity-Verlet kick and drift, the Langevin O step with its noise drawn on the device, the kinetic energy, the
+// end-of-step bookkeeping and the barostat (gn_npt_*: the volume move, the rescaling, the internal pressure, the cell guard).
 //
 // state int32 [2]: state[0] is the sticky "the stored neighbour list is stale" word of gn_radius_verify*, state[1] the number
 // of completed steps.  Every kernel here reads state[0] first and does nothing when it is set: a replay on a stale list moves
@@ -131,6 +131,122 @@ __global__ __launch_bounds__(1024) void md_finish_kernel(int* __restrict__ state
         for (int k = t; k < 9 * n_mol; k += 1024) stress_keep[k] = stress[k];
 }
 
+// ---- the barostat: isotropic stochastic cell rescaling in eps = ln V (Bernetti and Bussi, J. Chem. Phys. 153, 114107, 2020),
+// stated in include/gotennet_hip.h.  reason int32 [n_mol] holds WHY a box stopped the run (1: the cell outgrew the search
+// parameters, 2: a volume move beyond max_step); state[0] is the one sticky word all kernels are predicated on.
+// P_int = 2 K / (3 V) - tr(sigma) / 3 in fp64 from the fp32 inputs, rounded once
+__device__ __forceinline__ float npt_pressure(float ke, const float* __restrict__ sg, float vol) {
+    const double tr = ((double)sg[0] + (double)sg[4]) + (double)sg[8];
+    return (float)(2.0 * (double)ke / (3.0 * (double)vol) - tr / 3.0);
+}
+
+// One thread per box: the kept pressure of the step that is ending and row (counter mod log_len) of the (V, P) ring.
+// Runs BEFORE md_finish_kernel moves the counter.
+__global__ void npt_pressure_kernel(const float* __restrict__ ke, const float* __restrict__ stress,
+                                    const float* __restrict__ volume, int n_mol, float* __restrict__ pressure,
+                                    float* __restrict__ log, int log_len, const int* __restrict__ state) {
+    if (md_frozen(state)) return;
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_mol) return;
+    const float p = npt_pressure(ke[m], stress + 9 * (size_t)m, volume[m]);
+    pressure[m] = p;
+    if (log != nullptr && log_len > 0 && state != nullptr) {
+        float* row = log + ((size_t)((unsigned)state[1] % (unsigned)log_len) * (size_t)n_mol + (size_t)m) * 2;
+        row[0] = volume[m];
+        row[1] = p;
+    }
+}
+
+// d eps = -(beta / tau) (P0 - P) dt + sqrt(2 kT beta dt / (V tau)) xi.  (The volume equation of the paper carries a drift
+// kT beta / tau per unit time as well; written in eps = ln V it cancels against the Ito term -(1/2) (2 kT beta / (V tau)) V / V,
+// so the equation in eps has none.)  xi: the first normal of md_normal_pair(key, box, pair 0, draw 2, step); the key is not
+// read when kT == 0.
+__device__ __forceinline__ double npt_delta_eps(int m, const float* __restrict__ volume, const float* __restrict__ pressure,
+                                                double p0, double beta, double tau, double dt, double kT,
+                                                const long long* __restrict__ key, unsigned step) {
+    double de = -(beta / tau) * (p0 - (double)pressure[m]) * dt;
+    if (kT > 0.0) {
+        float xa, xb;
+        md_normal_pair(key, (unsigned)m, 0u, 2u, step, xa, xb);
+        de += sqrt(2.0 * kT * beta * dt / ((double)volume[m] * tau)) * (double)xa;
+    }
+    return de;
+}
+
+// ONE workgroup, a thread per box (strided beyond 1024 boxes).  First every box's move is held against max_step: a move that
+// is not finite or is larger stores reason 2 for its box and sets the sticky word, and then NO box is moved -- the cell array,
+// s and inv_s stay as they are.  Otherwise s = exp(d eps / 3) and 1 / s are rounded once to fp32 and the nine cell entries
+// are multiplied by s in fp32.
+__global__ __launch_bounds__(1024) void npt_barostat_kernel(float* __restrict__ cell, const float* __restrict__ volume,
+                                                            const float* __restrict__ pressure, int n_mol, double p0,
+                                                            double beta, double tau, double dt, double kT, double max_step,
+                                                            const long long* __restrict__ key, float* __restrict__ s_out,
+                                                            float* __restrict__ inv_s_out, int* __restrict__ state,
+                                                            int* __restrict__ reason) {
+    if (state[0] != 0) return;                         // (uniform: the word is written behind the barrier below only)
+    const unsigned step = (unsigned)state[1];
+    int bad = 0;
+    for (int m = threadIdx.x; m < n_mol; m += 1024) {
+        const double de = npt_delta_eps(m, volume, pressure, p0, beta, tau, dt, kT, key, step);
+        if (!(fabs(de) <= max_step)) {                 // (a NaN fails the comparison)
+            reason[m] = 2;
+            bad = 1;
+        }
+    }
+    if (__syncthreads_or(bad)) {
+        if (bad) state[0] = 1;
+        return;
+    }
+    for (int m = threadIdx.x; m < n_mol; m += 1024) {
+        const double sd = exp(npt_delta_eps(m, volume, pressure, p0, beta, tau, dt, kT, key, step) / 3.0);
+        const float s = (float)sd;
+        s_out[m] = s;
+        inv_s_out[m] = (float)(1.0 / sd);
+        float* c = cell + 9 * (size_t)m;
+        for (int k = 0; k < 9; ++k) c[k] *= s;
+    }
+}
+
+// pos *= s[box], vel *= 1 / s[box]: one thread per component (positions are scaled about the origin; a stored shift stays
+// valid, pos[j] - pos[i] + shift @ cell scales as a whole)
+__global__ void npt_rescale_kernel(float* __restrict__ pos, float* __restrict__ vel, const int64_t* __restrict__ batch,
+                                   const float* __restrict__ s, const float* __restrict__ inv_s, int n3, int n_mol,
+                                   const int* __restrict__ state) {
+    if (md_frozen(state)) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n3) return;
+    const int64_t b = batch[k / 3];
+    const int m = b < 0 ? 0 : (b >= n_mol ? n_mol - 1 : (int)b);        // (clamped as the searches clamp it)
+    pos[k] *= s[m];
+    vel[k] *= inv_s[m];
+}
+
+// Does the moved cell still satisfy what the search parameters of this run assume?  One thread per box, fp64, the formulas
+// of the host's check (graph.cell_widths): w_k = V / |a_i x a_j|; minimum image (img_range == NULL): w_k >= 2 cutoff;
+// else floor(cutoff / w_k + 1/2 + 2^-6) <= R_k.  A volume that is zero or not finite fails either way.
+__global__ void npt_cell_guard_kernel(const float* __restrict__ cell, int n_mol, double cutoff,
+                                      const int* __restrict__ img_range, int* __restrict__ state, int* __restrict__ reason) {
+    if (state[0] != 0) return;
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_mol) return;
+    const float* c = cell + 9 * (size_t)m;
+    const double a[3] = {c[0], c[1], c[2]}, b[3] = {c[3], c[4], c[5]}, d[3] = {c[6], c[7], c[8]};
+    const double f[3][3] = {{b[1] * d[2] - b[2] * d[1], b[2] * d[0] - b[0] * d[2], b[0] * d[1] - b[1] * d[0]},       // b x c
+                            {d[1] * a[2] - d[2] * a[1], d[2] * a[0] - d[0] * a[2], d[0] * a[1] - d[1] * a[0]},       // c x a
+                            {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]}};      // a x b
+    const double vol = fabs((a[0] * f[0][0] + a[1] * f[0][1]) + a[2] * f[0][2]);
+    bool ok = isfinite(vol) && vol != 0.0;
+    for (int k = 0; k < 3 && ok; ++k) {
+        const double w = vol / sqrt((f[k][0] * f[k][0] + f[k][1] * f[k][1]) + f[k][2] * f[k][2]);
+        if (img_range == nullptr) ok = w >= 2.0 * cutoff;
+        else ok = isfinite(w) && w > 0.0 && floor(cutoff / w + 0.5 + 0.015625) <= (double)img_range[3 * m + k];
+    }
+    if (!ok) {
+        reason[m] = 1;
+        state[0] = 1;
+    }
+}
+
 }  // namespace gn
 
 static bool md_table_ok(const int* z, const float* mass, int n_mass, int N) { return N == 0 || (z && mass && n_mass > 0); }
@@ -196,6 +312,52 @@ extern "C" int gn_md_finish(int* state, const float* force, float* force_keep, i
         return GN_ERR_BAD_ARG;
     hipLaunchKernelGGL(gn::md_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, state, force, force_keep, 3 * N,
                        energy, ke, energy_keep, stress, stress_keep, log, log_len, n_mol);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+static bool npt_count_ok(int n_mol) { return n_mol >= 0 && n_mol <= 0x7fffffff / 9; }
+
+extern "C" int gn_npt_pressure(const float* ke, const float* stress, const float* volume, int n_mol, float* pressure,
+                               float* log, int log_len, const int* state, void* stream) {
+    if (!npt_count_ok(n_mol) || log_len < 0 || (n_mol > 0 && (!ke || !stress || !volume || !pressure))) return GN_ERR_BAD_ARG;
+    if (n_mol == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::npt_pressure_kernel, dim3((n_mol + 63) / 64), dim3(64), 0, (hipStream_t)stream, ke, stress, volume,
+                       n_mol, pressure, log, log_len, state);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_npt_barostat(float* cell, const float* volume, const float* pressure, int n_mol, double p0, double beta,
+                               double tau, double dt, double kT, double max_step, const long long* key, float* s,
+                               float* inv_s, int* state, int* reason, void* stream) {
+    if (!npt_count_ok(n_mol) || !state || !(beta > 0.0) || !(tau > 0.0) || !(dt > 0.0) || !(kT >= 0.0) || !(max_step > 0.0) ||
+        (kT > 0.0 && !key) || (n_mol > 0 && (!cell || !volume || !pressure || !s || !inv_s || !reason)))
+        return GN_ERR_BAD_ARG;
+    if (n_mol == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::npt_barostat_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, cell, volume, pressure, n_mol, p0,
+                       beta, tau, dt, kT, max_step, key, s, inv_s, state, reason);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_npt_rescale(float* pos, float* vel, const int64_t* batch, const float* s, const float* inv_s, int N,
+                              int n_mol, const int* state, void* stream) {
+    if (N < 0 || N > 0x7fffffff / 3 || n_mol < 0 || (N > 0 && (n_mol < 1 || !pos || !vel || !batch || !s || !inv_s)))
+        return GN_ERR_BAD_ARG;
+    if (N == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::npt_rescale_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos, vel, batch, s,
+                       inv_s, 3 * N, n_mol, state);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_npt_cell_guard(const float* cell, int n_mol, double cutoff, const int* img_range, int* state, int* reason,
+                                 void* stream) {
+    if (!npt_count_ok(n_mol) || !state || !(cutoff > 0.0) || (n_mol > 0 && (!cell || !reason))) return GN_ERR_BAD_ARG;
+    if (n_mol == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::npt_cell_guard_kernel, dim3((n_mol + 63) / 64), dim3(64), 0, (hipStream_t)stream, cell, n_mol, cutoff,
+                       img_range, state, reason);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }

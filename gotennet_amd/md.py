@@ -1,9 +1,11 @@
-"""Molecular dynamics on the fused energy + force step: velocity Verlet, an optional Langevin thermostat, and a neighbour
-list that is CHECKED on the device inside every replayed step (kernels: csrc/gn_md.hip, gn_radius_verify* in csrc/gn_graph.hip).
+"""Molecular dynamics on the fused energy + force step: velocity Verlet, an optional Langevin thermostat, an optional
+barostat, and a neighbour list that is CHECKED on the device inside every replayed step (kernels: csrc/gn_md.hip,
+gn_radius_verify* in csrc/gn_graph.hip).
 
-One step, in both modes of ``MDRun``::
+One step, in both modes of ``MDRun`` (in brackets: with a thermostat; in braces: with a barostat)::
 
-    kick (previous forces) -> [Langevin half] -> drift -> [Langevin half] -> neighbour list -> model -> kick -> kinetic -> finish
+    kick (previous forces) -> [Langevin half] -> drift -> [Langevin half] -> {barostat -> rescale -> cell inverse -> cell guard}
+        -> neighbour list -> model -> kick -> kinetic -> {pressure} -> finish
 
 ``captured=True`` records that chain around ``CapturedStep``'s body into ONE hipGraph on a fixed edge list, with "neighbour
 list" = gn_radius_verify*: the search's own predicates, in the search's order, compared with the stored rows.  A row that
@@ -14,7 +16,30 @@ positions, records a new graph, finishes the interrupted step eagerly with the s
 reference of the captured mode -- the two trajectories agree bit for bit -- and the better choice for systems whose list
 changes in almost every step.
 
-The cell is fixed for a run: there is no barostat here.
+Constant pressure (``barostat=``): isotropic stochastic cell rescaling (Bernetti and Bussi, J. Chem. Phys. 153, 114107, 2020)
+written in eps = ln V.  Per box and step::
+
+    P_int = 2 K / (3 V) - tr(sigma) / 3        sigma = (1/V) dE/d(strain), the stress of ``EnergyForces(cell=)`` (tensile positive)
+    d_eps = -(beta_T / tau) (P0 - P_int) dt + sqrt(2 kT beta_T dt / (V tau)) xi
+    s     = exp(d_eps / 3):   cell <- s cell,   pos <- s pos,   vel <- vel / s
+
+xi is a standard normal, a pure function of (key, step, box): ``gn_md_noise(key, step, 2, n_mol)[:, 0]``.  The barostat moves
+the cell BEFORE the model runs, so forces, energy and stress at the end of a step belong to the (pos, cell) the driver
+reports; the pressure that drives a move is the kept one of the last completed step and so lags the move by one drift.  This
+is a first-order splitting, nothing more is claimed.  The move is formed by gn_npt_barostat from (kept pressure, volume, step
+counter, key) alone -- nothing the kick, the O steps or the drift touch -- so that kernel is launched at the head of the step:
+the trajectory is, bit for bit, that of the placement above, and a move larger than ``max_step`` (or a non-finite one) sets
+the sticky word before any atom has moved, leaves every cell as it is and stops the run with positions, velocities and cell
+of the last completed step (``RuntimeError``).  gn_npt_rescale, gn_cell_prepare and gn_npt_cell_guard follow the drift.
+
+The guard: the search parameters of a run (minimum image, or the image ranges of ``graph.image_ranges``) are conditions on
+the cell's perpendicular widths.  gn_npt_cell_guard checks the moved cell against the parameters IN USE on the device and
+sets the sticky word (reason 1) when they no longer hold; the rest of that replay, and every later one, advances nothing.  The
+host then runs ``graph.resolve_images`` on the current cell -- ``images="minimum"`` raises ``check_cell``'s ``ValueError``,
+"auto" / "all" give new ranges or raise below cutoff / 3 -- and repairs as for a stale list: new list at the frozen state
+(after the drift and the cell move of the first incomplete step), new recording, the rest of the step eagerly.  The eager
+mode launches the same guard and changes its ranges only when it fires, so both modes decide from the same bits.  Ranges
+larger than a grown cell needs cost candidates, never edges.
 """
 from __future__ import annotations
 
@@ -36,6 +61,11 @@ from .pipeline import CapturedStep, EnergyForces
 #: 4.184e6 m^2 / s^2 = 4.184e-4 Angstrom^2 / fs^2.  The thermostat's ``kT`` is in the model's energy unit.
 EV_ANGSTROM_AMU_FS = 9.648533212e-3
 KCAL_MOL_ANGSTROM_AMU_FS = 4.184e-4
+#: The barostat's ``pressure`` (and 1 / ``compressibility``) is in the model's energy unit per length^3.  1 bar = 1e5 J / m^3;
+#: in eV / Angstrom^3: 1e5 / 1.602176634e-19 (J per eV) * 1e-30 (m^3 per Angstrom^3) = 6.241509074e-7;  in
+#: kcal / (mol Angstrom^3): 1e5 * 6.02214076e23 (per mol) / 4184 (J per kcal) * 1e-30 = 1.439325e-5.
+BAR_EV_ANGSTROM3 = 1e5 / 1.602176634e-19 * 1e-30
+BAR_KCAL_MOL_ANGSTROM3 = 1e5 * 6.02214076e23 / 4184.0 * 1e-30
 
 
 def default_masses() -> torch.Tensor:
@@ -51,7 +81,45 @@ def langevin_coefficients(kT: float, gamma: float, h: float, force_scale: float 
     return c1, math.sqrt(float(kT) * float(force_scale) * (1.0 - c1 * c1))
 
 
-def validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images="minimum", check_every=1, log_len=1):
+_BAROSTAT_KEYS = ("pressure", "tau", "compressibility", "kT", "key", "max_step")
+
+
+def barostat_parameters(barostat: dict, thermostat: Optional[dict], cell) -> dict:
+    """``MDRun(barostat=)`` with its defaults filled in (kT and key from the thermostat, max_step 0.05), or ``ValueError``."""
+    if cell is None:
+        raise ValueError("barostat: a constant-pressure run needs a cell")
+    unknown = set(barostat) - set(_BAROSTAT_KEYS)
+    if unknown:
+        raise ValueError(f"barostat: unknown entries {sorted(unknown)}; known: {list(_BAROSTAT_KEYS)}")
+    missing = {"pressure", "tau", "compressibility"} - set(barostat)
+    if missing:
+        raise ValueError(f"barostat needs pressure, tau and compressibility; missing {sorted(missing)}")
+    out = dict(pressure=float(barostat["pressure"]), tau=float(barostat["tau"]),
+               compressibility=float(barostat["compressibility"]), max_step=float(barostat.get("max_step", 0.05)))
+    for name in ("tau", "compressibility", "max_step"):
+        if not (math.isfinite(out[name]) and out[name] > 0):
+            raise ValueError(f"barostat: {name} must be positive and finite, got {out[name]}")
+    if not math.isfinite(out["pressure"]):
+        raise ValueError(f"barostat: pressure must be finite, got {out['pressure']}")
+    kT = barostat.get("kT")
+    if kT is None:
+        if thermostat is None:
+            raise ValueError("barostat: kT is required when there is no thermostat (0: the deterministic weak-coupling limit)")
+        kT = thermostat["kT"]
+    kT = float(kT)
+    if not math.isfinite(kT) or kT < 0:
+        raise ValueError(f"barostat: kT must be finite and >= 0, got {kT}")
+    key = barostat.get("key")
+    if key is None and thermostat is not None:
+        key = thermostat["key"]
+    if kT > 0 and key is None:
+        raise ValueError("barostat: kT > 0 draws noise and needs a key (there is no thermostat to take it from)")
+    out.update(kT=kT, key=key)
+    return out
+
+
+def validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images="minimum", check_every=1, log_len=1,
+             barostat=None):
     """Everything ``MDRun`` refuses, before any launch -> (mass table fp32 on the CPU, ``graph.resolve_images``' result or None).
     Raises ``ValueError``.  Reads ``z`` (and ``cell``) on the host."""
     if not (math.isfinite(float(dt)) and float(dt) > 0):
@@ -75,6 +143,8 @@ def validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images="
         kT, gamma = float(thermostat["kT"]), float(thermostat["gamma"])
         if not (math.isfinite(kT) and math.isfinite(gamma)) or kT < 0 or gamma < 0:
             raise ValueError(f"thermostat: kT and gamma must be finite and >= 0, got kT={kT}, gamma={gamma}")
+    if barostat is not None:
+        barostat_parameters(barostat, thermostat, cell)
     if pos.requires_grad:
         raise ValueError("pos requires grad: the driver integrates plain tensors")
     if cell is not None and cell.requires_grad:
@@ -112,8 +182,8 @@ class _RecordedStep(CapturedStep):
         return super()._body()
 
     def _body(self):
-        self.md._pre(self.pos)
-        self.md._verify(self.pos, self.g)
+        self.md._pre(self.pos, self.cell)
+        self.md._verify(self.pos, self.g, self.cell)
         out = super()._body()
         self.md._post(*out)
         return out
@@ -145,24 +215,39 @@ class MDRun:
                    thermostat=dict(kT=0.0259, gamma=0.01, key=1234))
         md.run(1000)
         md.pos, md.vel, md.potential_energy, md.kinetic_energy, md.energy_log(), md.rebuilds
+        md.cell, md.volume, md.pressure, md.npt_log()              # periodic runs / runs with a barostat
 
     ``masses``: a table indexed by atomic number (default ``default_masses()``).  ``force_scale``: a = force_scale * F / m in
     the caller's units (``EV_ANGSTROM_AMU_FS``, ``KCAL_MOL_ANGSTROM_AMU_FS``; default 1: consistent units).  ``cell`` / ``images`` /
-    ``max_num_neighbors``: as ``graph.distance_pbc``; the cell is fixed for the run (no barostat).  ``thermostat``: None (NVE) or
+    ``max_num_neighbors``: as ``graph.distance_pbc``; the cell is fixed unless there is a barostat.  ``thermostat``: None (NVE) or
     ``dict(kT=, gamma=, key=)``: a Langevin O step of half a time step on either side of the drift, its noise a pure function
     of (key, step, half, atom, component) -- ``gn_md_noise`` reproduces it.  ``check_every``: replays between two host reads of
     the stale-list word (the trajectory does not depend on it).  ``log_len``: rows of the (potential, kinetic) energy ring
     buffer.  ``captured=False``: the eager reference (module docstring).
 
+    ``barostat``: None (the cell is fixed: the launches and the bits of a run without this argument) or
+    ``dict(pressure=, tau=, compressibility=, kT=None, key=None, max_step=0.05)``: isotropic stochastic cell rescaling on the
+    device, inside the replay (module docstring: the scheme, its placement -- a first-order splitting, the driving pressure lags
+    the move by one drift -- and the guard).  ``pressure``: the target in the model's energy unit per length^3
+    (``BAR_EV_ANGSTROM3``, ``BAR_KCAL_MOL_ANGSTROM3``); ``tau``: the relaxation time in the caller's time unit;
+    ``compressibility``: beta_T in inverse pressure units; ``kT``: default the thermostat's, required without one, 0 = the
+    deterministic weak-coupling limit; ``key``: an int or a pair, default the thermostat's, required when kT > 0 without one;
+    ``max_step``: the largest |d ln V| of one step -- a larger (or non-finite) one stops the run with ``RuntimeError`` at the
+    last completed step.  A cell that shrinks below what ``images`` allows raises ``graph.resolve_images``' ``ValueError``
+    from ``run``.
+
     Refused with ``ValueError`` before any launch: dt <= 0, a negative or missing mass, kT < 0, gamma < 0, a cell that
-    ``graph.resolve_images`` refuses, ``pos`` or ``cell`` requiring grad."""
+    ``graph.resolve_images`` refuses, ``pos`` or ``cell`` requiring grad; a barostat without a cell, with entries missing, with
+    tau, compressibility or max_step not positive and finite, a non-finite pressure, kT < 0, or kT > 0 without a key."""
 
     def __init__(self, ef: EnergyForces, z: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, n_mol: int, dt: float,
                  masses=None, force_scale: float = 1.0, vel: Optional[torch.Tensor] = None,
                  cell: Optional[torch.Tensor] = None, images: str = "minimum", max_num_neighbors: int = 32,
-                 thermostat: Optional[dict] = None, check_every: int = 1, log_len: int = 1024, captured: bool = True):
+                 thermostat: Optional[dict] = None, check_every: int = 1, log_len: int = 1024, captured: bool = True,
+                 barostat: Optional[dict] = None):
         cutoff = float(ef.rep.cutoff)
-        table, ranges = validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images, check_every, log_len)
+        table, ranges = validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images, check_every, log_len,
+                                 barostat)
         dev = pos.device
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
         self.ef, self.n_mol, self.N, self.images = ef, int(n_mol), pos.shape[0], images
@@ -187,6 +272,15 @@ class MDRun:
         self._stress = torch.empty((self.n_mol, 3, 3), **f32) if cell is not None else None
         self._log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
         self._row_flag, self._changed = torch.zeros(self.N, **i32), torch.zeros(self.n_mol, **i32)
+        self._baro = None
+        if barostat is not None:
+            self._baro = b = barostat_parameters(barostat, thermostat, cell)
+            self._cell = self._cell.clone()                    # it moves in place: never the caller's tensor
+            self._baro_key = torch.tensor(_key_words(b["key"]), dtype=torch.int64, device=dev) if b["kT"] > 0 else None
+            self._volume, self._p = torch.empty(self.n_mol, **f32), torch.empty(self.n_mol, **f32)
+            self._s, self._inv_s = torch.ones(self.n_mol, **f32), torch.ones(self.n_mol, **f32)
+            self._reason = torch.zeros(self.n_mol, **i32)      # why a box set the sticky word: 1 cell guard, 2 max_step
+            self._npt_log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
         self._done, self.rebuilds, self._fresh = 0, 0, False
         start = pos.detach().to(**f32).contiguous()
         lst = self._list(start)
@@ -207,6 +301,9 @@ class MDRun:
         if self._stress is not None:
             self._stress.copy_(out[2])
         self._kinetic()
+        if self._baro is not None:
+            graph.cell_prepare(self._cell, self._inv_cell, self._volume)
+            self._pressure(self._stress, ring=False)
 
     # ---- the pieces of a step: the same launches whether recorded or eager -----------------------------------------
     def _list(self, pos):
@@ -231,37 +328,71 @@ class MDRun:
         call("gn_md_kinetic", ptr(self._vel), ptr(self._z32), ptr(self._mass), self._mass.numel(), ptr(self._mol_ptr), self.N,
              self.n_mol, float(self.force_scale), ptr(self._ke), ptr(self._state), engine._stream())
 
-    def _pre(self, pos):
+    def _pressure(self, stress, ring=True):
+        call("gn_npt_pressure", ptr(self._ke), ptr(stress), ptr(self._volume), self.n_mol, ptr(self._p),
+             ptr(self._npt_log) if ring else None, self.log_len, ptr(self._state), engine._stream())
+
+    def _pre(self, pos, cell=None):
+        """Everything before the neighbour list.  ``pos`` / ``cell``: the buffers the step reads (a recording passes its own)."""
+        b = self._baro
+        if b is not None:          # the move and its refusal, from the kept pressure: at the head of the step (module docstring)
+            call("gn_npt_barostat", ptr(cell), ptr(self._volume), ptr(self._p), self.n_mol, b["pressure"], b["compressibility"],
+                 b["tau"], self.dt, b["kT"], b["max_step"], ptr(self._baro_key), ptr(self._s), ptr(self._inv_s), ptr(self._state),
+                 ptr(self._reason), engine._stream())
         self._kick(self._f)
         self._langevin(0)
         call("gn_md_drift", ptr(pos), ptr(self._vel), self.N, float(self.dt), ptr(self._state), engine._stream())
         self._langevin(1)
+        if b is not None:
+            call("gn_npt_rescale", ptr(pos), ptr(self._vel), ptr(self._batch), ptr(self._s), ptr(self._inv_s), self.N, self.n_mol,
+                 ptr(self._state), engine._stream())
+            graph.cell_prepare(cell, self._inv_cell, self._volume)
+            call("gn_npt_cell_guard", ptr(cell), self.n_mol, self.cutoff, ptr(self._ranges), ptr(self._state), ptr(self._reason),
+                 engine._stream())
 
-    def _verify(self, pos, g):
+    def _verify(self, pos, g, cell=None):
         graph.verify_list(pos, self._batch, self._mol_ptr, self.n_mol, g.rowptr, g.src, self.cutoff, self.max_num_neighbors,
-                          self._row_flag, self._changed, self._state, shift=g.shift, cell=self._cell,
+                          self._row_flag, self._changed, self._state, shift=g.shift, cell=cell,
                           inv_cell=self._inv_cell, image_range=self._ranges)
 
     def _post(self, energy, forces, stress=None):
         self._kick(forces)
         self._kinetic()
+        if self._baro is not None:
+            self._pressure(stress)
         call("gn_md_finish", ptr(self._state), ptr(forces), ptr(self._f), self.N, ptr(energy), ptr(self._ke), ptr(self._e),
              ptr(stress), ptr(self._stress), ptr(self._log), self.log_len, self.n_mol, engine._stream())
 
     # ---- captured mode ---------------------------------------------------------------------------------------------
     def _record(self, lst):
-        """Record the step on the list ``lst`` and move the positions into its static buffer.  The sticky word is held at 1
-        meanwhile (the recording's warm-up runs advance nothing) and LEFT at 1: the caller clears it."""
+        """Record the step on the list ``lst`` and move the positions into its static buffer; the recording's clone of the
+        current cell becomes the driver's cell.  The sticky word is held at 1 meanwhile (the recording's warm-up runs advance
+        nothing) and LEFT at 1: the caller clears it."""
         self._state[:1].fill_(1)
         pos = self._pos
         self._step = _RecordedStep(self, lst[0], lst[1])
         self._step.pos.copy_(pos)
-        self._pos = self._step.pos
+        self._pos, self._cell = self._step.pos, self._step.cell
         self._fresh = True
 
+    def _guarded(self):
+        """The sticky word is set: was it the barostat?  Reason 2 (a move beyond ``max_step``) ends the run; reason 1 (the cell
+        outgrew the search parameters) gets new ones from ``graph.resolve_images`` on the current cell, or what that raises.
+        The caller repairs the list next."""
+        if self._baro is None:
+            return
+        reason = self._reason.tolist()
+        if 2 in reason:
+            raise RuntimeError(f"barostat: box {reason.index(2)} asks for a volume move |d ln V| that is not finite or exceeds "
+                               f"max_step = {self._baro['max_step']} in step {self._done + 1}; the run stops at step {self._done}")
+        if 1 in reason:
+            ranges = graph.resolve_images(self._cell, self.cutoff, self.images)
+            self._ranges = None if ranges is None else ranges.expand(self.n_mol, 3).contiguous().to(self._cell.device)
+            self._reason.zero_()
+
     def _repair(self):
-        """The sticky word is set: positions and velocities are those after the drift of the first incomplete step.  New
-        list there, new graph (the old one is dropped first: one alive at a time), then the rest of that step eagerly."""
+        """The sticky word is set: positions and velocities (and the cell) are those after the drift (and the cell move) of the
+        first incomplete step.  New list there, new graph (the old one is dropped first: one alive at a time), then the rest of that step eagerly."""
         lst = self._list(self._pos)
         torch.cuda.synchronize()
         self._step = None
@@ -277,14 +408,17 @@ class MDRun:
         replay of a newly recorded graph and at the end (a stream synchronisation each)."""
         if not self.captured:
             for _ in range(int(n)):
-                self._pre(self._pos)
+                self._pre(self._pos, self._cell)
+                if self._baro is not None and self._state.tolist()[0]:      # the guard's verdict, from the guard's kernel
+                    self._guarded()
+                    self._state[:1].zero_()
                 lst = self._list(self._pos)
                 if not (torch.equal(lst[0], self._lst[0]) and (lst[1] is None or torch.equal(lst[1], self._lst[1]))):
                     self.rebuilds += 1
                 self._lst = lst
                 self._eager.set_list(*lst)
                 self._post(*self._eager._body())
-            self._done += int(n)
+                self._done += 1
             return self
         target = self._done + int(n)
         while self._done < target:
@@ -294,6 +428,7 @@ class MDRun:
             self._fresh = False
             stale, self._done = self._state.tolist()             # (the synchronisation)
             if stale:
+                self._guarded()
                 self._repair()
         return self
 
@@ -328,8 +463,45 @@ class MDRun:
             raise ValueError("stress: this run has no cell")
         return self._stress.clone()
 
-    def energy_log(self) -> torch.Tensor:
-        """[k, n_mol, 2]: (potential, kinetic) energy after each of the last k = min(step, log_len) steps, oldest first."""
+    @property
+    def cell(self) -> torch.Tensor:
+        """[n_mol, 3, 3]: the current cell (periodic runs)."""
+        if self._cell is None:
+            raise ValueError("cell: this run has no cell")
+        return self._cell.clone()
+
+    @property
+    def volume(self) -> torch.Tensor:
+        """[n_mol]: |det cell| (gn_cell_prepare's)."""
+        if self._cell is None:
+            raise ValueError("volume: this run has no cell")
+        return self._volume.clone() if self._baro is not None else graph.cell_prepare(self._cell)[1]
+
+    @property
+    def pressure(self) -> torch.Tensor:
+        """[n_mol]: the internal pressure 2 K / (3 V) - tr(stress) / 3 of the last completed step (of the start before the
+        first), in the model's energy unit per length^3."""
+        if self._cell is None:
+            raise ValueError("pressure: this run has no cell")
+        if self._baro is not None:
+            return self._p.clone()
+        p, vol = torch.empty(self.n_mol, dtype=torch.float32, device=self._ke.device), self.volume
+        call("gn_npt_pressure", ptr(self._ke), ptr(self._stress), ptr(vol), self.n_mol, ptr(p), None, 0, None,
+             engine._stream())
+        return p
+
+    def _ring(self, log):
         k = min(self._done, self.log_len)
         rows = [(s % self.log_len) for s in range(self._done - k, self._done)]
-        return self._log[torch.tensor(rows, dtype=torch.long, device=self._log.device)]
+        return log[torch.tensor(rows, dtype=torch.long, device=log.device)]
+
+    def energy_log(self) -> torch.Tensor:
+        """[k, n_mol, 2]: (potential, kinetic) energy after each of the last k = min(step, log_len) steps, oldest first."""
+        return self._ring(self._log)
+
+    def npt_log(self) -> torch.Tensor:
+        """[k, n_mol, 2]: (volume, internal pressure) after each of the last k = min(step, log_len) steps, oldest first (runs
+        with a barostat)."""
+        if self._baro is None:
+            raise ValueError("npt_log: this run has no barostat")
+        return self._ring(self._npt_log)

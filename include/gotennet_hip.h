@@ -616,6 +616,37 @@ int gn_md_kinetic(const float* vel, const int* z, const float* mass, int n_mass,
 int gn_md_finish(int* state, const float* force, float* force_keep, int N, const float* energy, const float* ke,
                  float* energy_keep, const float* stress, float* stress_keep, float* log, int log_len, int n_mol,
                  void* stream);
+/* Constant pressure: isotropic stochastic cell rescaling in eps = ln V (Bernetti and Bussi, J. Chem. Phys. 153, 114107,
+ * 2020), one move per step, predicated on state[0] like the kernels above.  reason int32 [n_mol] says why a box stopped
+ * the run (plain stores of one value, never cleared on the device): 1 = the moved cell no longer satisfies the search
+ * parameters, 2 = a move beyond max_step.
+ * gn_npt_pressure, one thread per box: pressure[m] = 2 ke[m] / (3 volume[m]) - trace(stress[m]) / 3 (stress [n_mol, 9] =
+ * (1/V) dE/d(strain), tensile positive: gn_virial's), formed in fp64 and rounded once; with k = state[1], row k % log_len of
+ * log [log_len, n_mol, 2] receives (volume[m], pressure[m]) (log NULL or state NULL: no row; state NULL: never frozen).
+ * Launched before gn_md_finish moves the counter. */
+int gn_npt_pressure(const float* ke, const float* stress, const float* volume, int n_mol, float* pressure, float* log,
+                    int log_len, const int* state, void* stream);
+/* gn_npt_barostat, one workgroup, a thread per box, fp64 from the fp32 inputs:
+ *   d_eps = -(beta / tau) (p0 - pressure[m]) dt + sqrt(2 kT beta dt / (volume[m] tau)) xi,
+ * xi = the first normal of the noise above with atom = m, pair 0, draw 2, step = state[1] (gn_md_noise(key, step, 2,
+ * n_mol)[:, 0]); kT == 0 is the deterministic weak-coupling limit and `key` (a DEVICE pointer, as above) is not read.
+ * s[m] = fp32(exp(d_eps / 3)), inv_s[m] = fp32(1 / exp(d_eps / 3)), and the nine entries of cell[m] are multiplied by s[m] in
+ * fp32.  If some box's d_eps is not finite or |d_eps| > max_step, reason[m] = 2 for every such box, state[0] = 1 and
+ * NOTHING else is written for any box.  Reads none of pos / vel / force: where in the step it runs before gn_npt_rescale
+ * does not change a bit. */
+int gn_npt_barostat(float* cell, const float* volume, const float* pressure, int n_mol, double p0, double beta, double tau,
+                    double dt, double kT, double max_step, const long long* key, float* s, float* inv_s, int* state,
+                    int* reason, void* stream);
+/* pos[a] *= s[batch[a]], vel[a] *= inv_s[batch[a]] in fp32, one thread per component (batch entries clamped to
+ * [0, n_mol)); state NULL: never frozen. */
+int gn_npt_rescale(float* pos, float* vel, const int64_t* batch, const float* s, const float* inv_s, int N, int n_mol,
+                   const int* state, void* stream);
+/* gn_npt_cell_guard, one thread per box, fp64: the perpendicular widths w_k = V / |a_i x a_j| of cell[m] against the search
+ * parameters in use -- img_range NULL (the minimum-image kernels): every w_k >= 2 cutoff; else
+ * floor(cutoff / w_k + 1/2 + 2^-6) <= img_range[m, k] -- and the volume finite and non-zero.  A violation stores
+ * reason[m] = 1 and state[0] = 1. */
+int gn_npt_cell_guard(const float* cell, int n_mol, double cutoff, const int* img_range, int* state, int* reason,
+                      void* stream);
 
 /* ---- parameter gradients (first-order training: a loss on energies and / or (h, X)) -------------
  * Every reduction below runs in a fixed order and uses no atomics: identical inputs give identical bits. */
