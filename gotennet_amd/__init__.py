@@ -7,3 +7,11 @@ from .layers import CosineCutoff  # noqa: F401
 from .md import MDRun  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    """``gotennet_amd.Relax`` (relax.py), imported on first use: the package itself loads what it loaded before."""
+    if name == "Relax":
+        from .relax import Relax
+        return Relax
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -208,7 +208,129 @@ class _EagerStep:
         self.g.csc()
 
 
-class MDRun:
+class _ListDriver:
+    """What ``MDRun`` and ``relax.Relax`` share, once: the neighbour search, the device check of the stored list, the
+    record / repair / replay loop and the handling of the sticky word.  A driver supplies ``_pre(pos, cell)`` (everything before
+    the neighbour list) and ``_post(energy, forces[, stress])`` (everything after the model) -- the protocol ``_RecordedStep`` and
+    ``_EagerStep`` talk to -- and may override ``_guarded`` (the sticky word is set: was it something other than the list?),
+    ``_after_pre`` (eager mode, between ``_pre`` and the search) and ``_looked`` (the host has just read the device state: True
+    ends ``run`` early)."""
+
+    def _setup(self, ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured):
+        dev = pos.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.ef, self.n_mol, self.N, self.images = ef, int(n_mol), pos.shape[0], images
+        self.cutoff, self.max_num_neighbors = float(ef.rep.cutoff), int(max_num_neighbors)
+        self.captured, self.check_every = bool(captured), int(check_every)
+        self._z, self._z32 = z, z.to(torch.int32).contiguous()
+        self._batch = batch.to(torch.int64).contiguous()
+        self._mol_ptr = molecule_ptr(self._batch, self.n_mol)
+        self._cell = self._inv_cell = self._ranges = None
+        if cell is not None:
+            self._cell, self._inv_cell, self._ranges = graph.box_arrays(cell, ranges, self.n_mol, dev)
+        self._state = torch.zeros(2, **i32)                       # {stale list (sticky), completed steps}
+        self._row_flag, self._changed = torch.zeros(self.N, **i32), torch.zeros(self.n_mol, **i32)
+        self._done, self.rebuilds, self._fresh = 0, 0, False
+
+    def _start(self, start):
+        """The first list and the first model evaluation at ``start`` -> (energy, forces[, stress]) of the step's own buffers."""
+        lst = self._list(start)
+        if self.captured:
+            self._step, self._pos = None, start
+            self._record(lst)
+            self._state[:1].zero_()
+            with torch.no_grad():
+                return self._step.model()
+        self._pos = start.clone()
+        self._eager, self._lst = _EagerStep(self), lst
+        self._eager.set_list(*lst)
+        with torch.no_grad():
+            return self._eager._body()
+
+    def _list(self, pos):
+        """(edge_index, edge_shift or None) of ``pos``: the project's own search (one host read of the edge count)."""
+        if self._cell is None:
+            return graph.distance(pos, self._batch, self.cutoff, self.max_num_neighbors)[0], None
+        ei, _, _, sh = graph.distance_pbc(pos, self._batch, self._cell, self.cutoff, self.max_num_neighbors, n_mol=self.n_mol,
+                                          check=False, image_range=self._ranges)
+        return ei, sh
+
+    def _verify(self, pos, g, cell=None):
+        graph.verify_list(pos, self._batch, self._mol_ptr, self.n_mol, g.rowptr, g.src, self.cutoff, self.max_num_neighbors,
+                          self._row_flag, self._changed, self._state, shift=g.shift, cell=cell,
+                          inv_cell=self._inv_cell, image_range=self._ranges)
+
+    def _record(self, lst):
+        """Record the step on the list ``lst`` and move the positions into its static buffer; the recording's clone of the
+        current cell becomes the driver's cell.  The sticky word is held at 1 meanwhile (the recording's warm-up runs advance
+        nothing) and LEFT at 1: the caller clears it."""
+        self._state[:1].fill_(1)
+        pos = self._pos
+        self._step = _RecordedStep(self, lst[0], lst[1])
+        self._step.pos.copy_(pos)
+        self._pos, self._cell = self._step.pos, self._step.cell
+        self._fresh = True
+
+    def _guarded(self):
+        pass
+
+    def _after_pre(self):
+        pass
+
+    def _looked(self) -> bool:
+        return False
+
+    def _repair(self):
+        """The sticky word is set: the state is the one after the move (MD: the drift and the cell move) of the first incomplete
+        step.  New list there, new graph (the old one is dropped first: one alive at a time), then the rest of that step eagerly."""
+        lst = self._list(self._pos)
+        torch.cuda.synchronize()
+        self._step = None
+        self._record(lst)
+        self._state[:1].zero_()
+        self._post(*self._step.model())
+        self.rebuilds += 1
+        self._done += 1
+
+    @torch.no_grad()
+    def run(self, n: int):
+        """Advance ``n`` steps.  Captured: the host reads the device state after every ``check_every`` replays, after the first
+        replay of a newly recorded graph and at the end (a stream synchronisation each)."""
+        if not self.captured:
+            for _ in range(int(n)):
+                self._pre(self._pos, self._cell)
+                self._after_pre()
+                lst = self._list(self._pos)
+                if not (torch.equal(lst[0], self._lst[0]) and (lst[1] is None or torch.equal(lst[1], self._lst[1]))):
+                    self.rebuilds += 1
+                self._lst = lst
+                self._eager.set_list(*lst)
+                self._post(*self._eager._body())
+                self._done += 1
+                if self._looked():
+                    break
+            return self
+        target = self._done + int(n)
+        while self._done < target:
+            burst = 1 if self._fresh else min(self.check_every, target - self._done)
+            for _ in range(burst):
+                self._step.graph.replay()
+            self._fresh = False
+            stale, self._done = self._state.tolist()             # (the synchronisation)
+            if stale:
+                self._guarded()
+                self._repair()
+            if self._looked():
+                break
+        return self
+
+    def _ring(self, log):
+        k = min(self.step, self.log_len)
+        rows = [(s % self.log_len) for s in range(self.step - k, self.step)]
+        return log[torch.tensor(rows, dtype=torch.long, device=log.device)]
+
+
+class MDRun(_ListDriver):
     """A trajectory of ``ef``'s model (``pipeline.EnergyForces``) from ``pos`` (and ``vel``, default zero) with time step ``dt``.
 
         md = MDRun(EnergyForces(rep, head, check_edges=False), z, pos, batch, n_mol, dt=0.5, force_scale=EV_ANGSTROM_AMU_FS,
@@ -245,33 +367,22 @@ class MDRun:
                  cell: Optional[torch.Tensor] = None, images: str = "minimum", max_num_neighbors: int = 32,
                  thermostat: Optional[dict] = None, check_every: int = 1, log_len: int = 1024, captured: bool = True,
                  barostat: Optional[dict] = None):
-        cutoff = float(ef.rep.cutoff)
-        table, ranges = validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images, check_every, log_len,
-                                 barostat)
+        table, ranges = validate(z, pos, dt, masses, force_scale, thermostat, cell, float(ef.rep.cutoff), images, check_every,
+                                 log_len, barostat)
         dev = pos.device
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-        self.ef, self.n_mol, self.N, self.images = ef, int(n_mol), pos.shape[0], images
-        self.cutoff, self.max_num_neighbors = cutoff, int(max_num_neighbors)
-        self.dt, self.force_scale, self.captured = float(dt), float(force_scale), bool(captured)
-        self.check_every, self.log_len = int(check_every), int(log_len)
-        self._z, self._z32 = z, z.to(torch.int32).contiguous()
-        self._batch = batch.to(torch.int64).contiguous()
-        self._mol_ptr = molecule_ptr(self._batch, self.n_mol)
+        self._setup(ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured)
+        self.dt, self.force_scale, self.log_len = float(dt), float(force_scale), int(log_len)
         self._mass = table.to(dev)
-        self._cell = self._inv_cell = self._ranges = None
-        if cell is not None:
-            self._cell, self._inv_cell, self._ranges = graph.box_arrays(cell, ranges, self.n_mol, dev)
         self._thermo = None
         if thermostat is not None:
             c1, c2 = langevin_coefficients(thermostat["kT"], thermostat["gamma"], 0.5 * self.dt, self.force_scale)
             self._thermo = (c1, c2, torch.tensor(_key_words(thermostat["key"]), dtype=torch.int64, device=dev))
         self._vel = torch.zeros((self.N, 3), **f32) if vel is None else vel.detach().to(**f32).clone().contiguous()
-        self._state = torch.zeros(2, **i32)                       # {stale list (sticky), completed steps}
         self._f = torch.empty((self.N, 3), **f32)                 # forces of the last completed step: the next kick's
         self._e, self._ke = torch.empty(self.n_mol, **f32), torch.empty(self.n_mol, **f32)
         self._stress = torch.empty((self.n_mol, 3, 3), **f32) if cell is not None else None
         self._log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
-        self._row_flag, self._changed = torch.zeros(self.N, **i32), torch.zeros(self.n_mol, **i32)
         self._baro = None
         if barostat is not None:
             self._baro = b = barostat_parameters(barostat, thermostat, cell)
@@ -281,21 +392,7 @@ class MDRun:
             self._s, self._inv_s = torch.ones(self.n_mol, **f32), torch.ones(self.n_mol, **f32)
             self._reason = torch.zeros(self.n_mol, **i32)      # why a box set the sticky word: 1 cell guard, 2 max_step
             self._npt_log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
-        self._done, self.rebuilds, self._fresh = 0, 0, False
-        start = pos.detach().to(**f32).contiguous()
-        lst = self._list(start)
-        if self.captured:
-            self._step, self._pos = None, start
-            self._record(lst)
-            self._state[:1].zero_()
-            with torch.no_grad():
-                out = self._step.model()
-        else:
-            self._pos = start.clone()
-            self._eager, self._lst = _EagerStep(self), lst
-            self._eager.set_list(*lst)
-            with torch.no_grad():
-                out = self._eager._body()
+        out = self._start(pos.detach().to(**f32).contiguous())
         self._f.copy_(out[1])
         self._e.copy_(out[0].reshape(-1))
         if self._stress is not None:
@@ -306,14 +403,6 @@ class MDRun:
             self._pressure(self._stress, ring=False)
 
     # ---- the pieces of a step: the same launches whether recorded or eager -----------------------------------------
-    def _list(self, pos):
-        """(edge_index, edge_shift or None) of ``pos``: the project's own search (one host read of the edge count)."""
-        if self._cell is None:
-            return graph.distance(pos, self._batch, self.cutoff, self.max_num_neighbors)[0], None
-        ei, _, _, sh = graph.distance_pbc(pos, self._batch, self._cell, self.cutoff, self.max_num_neighbors, n_mol=self.n_mol,
-                                          check=False, image_range=self._ranges)
-        return ei, sh
-
     def _kick(self, force):
         call("gn_md_kick", ptr(self._vel), ptr(force), ptr(self._z32), ptr(self._mass), self._mass.numel(), self.N,
              float(0.5 * self.dt * self.force_scale), ptr(self._state), engine._stream())
@@ -350,11 +439,6 @@ class MDRun:
             call("gn_npt_cell_guard", ptr(cell), self.n_mol, self.cutoff, ptr(self._ranges), ptr(self._state), ptr(self._reason),
                  engine._stream())
 
-    def _verify(self, pos, g, cell=None):
-        graph.verify_list(pos, self._batch, self._mol_ptr, self.n_mol, g.rowptr, g.src, self.cutoff, self.max_num_neighbors,
-                          self._row_flag, self._changed, self._state, shift=g.shift, cell=cell,
-                          inv_cell=self._inv_cell, image_range=self._ranges)
-
     def _post(self, energy, forces, stress=None):
         self._kick(forces)
         self._kinetic()
@@ -362,18 +446,6 @@ class MDRun:
             self._pressure(stress)
         call("gn_md_finish", ptr(self._state), ptr(forces), ptr(self._f), self.N, ptr(energy), ptr(self._ke), ptr(self._e),
              ptr(stress), ptr(self._stress), ptr(self._log), self.log_len, self.n_mol, engine._stream())
-
-    # ---- captured mode ---------------------------------------------------------------------------------------------
-    def _record(self, lst):
-        """Record the step on the list ``lst`` and move the positions into its static buffer; the recording's clone of the
-        current cell becomes the driver's cell.  The sticky word is held at 1 meanwhile (the recording's warm-up runs advance
-        nothing) and LEFT at 1: the caller clears it."""
-        self._state[:1].fill_(1)
-        pos = self._pos
-        self._step = _RecordedStep(self, lst[0], lst[1])
-        self._step.pos.copy_(pos)
-        self._pos, self._cell = self._step.pos, self._step.cell
-        self._fresh = True
 
     def _guarded(self):
         """The sticky word is set: was it the barostat?  Reason 2 (a move beyond ``max_step``) ends the run; reason 1 (the cell
@@ -390,47 +462,10 @@ class MDRun:
             self._ranges = None if ranges is None else ranges.expand(self.n_mol, 3).contiguous().to(self._cell.device)
             self._reason.zero_()
 
-    def _repair(self):
-        """The sticky word is set: positions and velocities (and the cell) are those after the drift (and the cell move) of the
-        first incomplete step.  New list there, new graph (the old one is dropped first: one alive at a time), then the rest of that step eagerly."""
-        lst = self._list(self._pos)
-        torch.cuda.synchronize()
-        self._step = None
-        self._record(lst)
-        self._state[:1].zero_()
-        self._post(*self._step.model())
-        self.rebuilds += 1
-        self._done += 1
-
-    @torch.no_grad()
-    def run(self, n: int) -> "MDRun":
-        """Advance ``n`` steps.  Captured: the host reads the device state after every ``check_every`` replays, after the first
-        replay of a newly recorded graph and at the end (a stream synchronisation each)."""
-        if not self.captured:
-            for _ in range(int(n)):
-                self._pre(self._pos, self._cell)
-                if self._baro is not None and self._state.tolist()[0]:      # the guard's verdict, from the guard's kernel
-                    self._guarded()
-                    self._state[:1].zero_()
-                lst = self._list(self._pos)
-                if not (torch.equal(lst[0], self._lst[0]) and (lst[1] is None or torch.equal(lst[1], self._lst[1]))):
-                    self.rebuilds += 1
-                self._lst = lst
-                self._eager.set_list(*lst)
-                self._post(*self._eager._body())
-                self._done += 1
-            return self
-        target = self._done + int(n)
-        while self._done < target:
-            burst = 1 if self._fresh else min(self.check_every, target - self._done)
-            for _ in range(burst):
-                self._step.graph.replay()
-            self._fresh = False
-            stale, self._done = self._state.tolist()             # (the synchronisation)
-            if stale:
-                self._guarded()
-                self._repair()
-        return self
+    def _after_pre(self):
+        if self._baro is not None and self._state.tolist()[0]:      # the guard's verdict, from the guard's kernel
+            self._guarded()
+            self._state[:1].zero_()
 
     # ---- state and queries -----------------------------------------------------------------------------------------
     @property
@@ -489,11 +524,6 @@ class MDRun:
         call("gn_npt_pressure", ptr(self._ke), ptr(self._stress), ptr(vol), self.n_mol, ptr(p), None, 0, None,
              engine._stream())
         return p
-
-    def _ring(self, log):
-        k = min(self._done, self.log_len)
-        rows = [(s % self.log_len) for s in range(self._done - k, self._done)]
-        return log[torch.tensor(rows, dtype=torch.long, device=log.device)]
 
     def energy_log(self) -> torch.Tensor:
         """[k, n_mol, 2]: (potential, kinetic) energy after each of the last k = min(step, log_len) steps, oldest first."""

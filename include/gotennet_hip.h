@@ -648,6 +648,43 @@ int gn_npt_rescale(float* pos, float* vel, const int64_t* batch, const float* s,
 int gn_npt_cell_guard(const float* cell, int n_mol, double cutoff, const int* img_range, int* state, int* reason,
                       void* stream);
 
+/* ---- FIRE relaxation around a recorded energy + force step (gotennet_amd/relax.py; Bitzek et al., PRL 97, 170201, the
+ * variant ASE's FIRE implements, unit masses) ----------------------------------------------------------------------
+ * `state` is the pair above; plan, move and finish read state[0] first and do NOTHING when it is set.  Per-molecule state,
+ * caller-allocated, [n_mol] each: dt fp32 (time step), alpha fp32 (mixing coefficient), n_pos int32 (steps since the last
+ * P <= 0; -1: no step taken yet), status int32 (0 active, 1 converged, 2 a force that is not finite; 1 and 2 are sticky on
+ * the device), converged_at int32 (state[1] when the status left 0; -1 until then).  fixed uint8 [N] (NULL: none) marks
+ * frozen atoms: their force counts as zero in every reduction and they never move.  mol_ptr int32 [n_mol + 1] of
+ * gn_molecule_ptr; every index derived from it is clamped to [0, N].  One workgroup of 256 threads per molecule (finish: one
+ * workgroup), no atomics, fixed-order sums, plain stores: identical inputs give identical bits. */
+/* out[m] = max over the free atoms of |force_a| (|f|^2 accumulated x, y, z in fp32, then sqrtf); 0 for an empty molecule. */
+int gn_fire_fmax(const float* force, const unsigned char* fixed, const int* mol_ptr, int N, int n_mol, float* out,
+                 void* stream);
+/* The decision of step k = state[1], from the KEPT forces and the velocities.  Over the free atoms: P = sum f.v,
+ * ff = sum |f|^2, vv = sum |v|^2 in fp64 from the fp32 inputs (products included), fm2 = max |f_a|^2 as gn_fire_fmax forms
+ * it.  Every molecule writes row k % log_len of log [log_len, n_mol, 2] = (energy_keep[m], sqrtf(fm2)): the state BEFORE the
+ * move of step k (log NULL or log_len 0: no row).  A molecule whose status is not 0 writes coef[m][3] = 0 and nothing else.
+ * Otherwise: fm2 not finite -> status 2, converged_at = k, no move;  fm2 <= fmax^2 (compared in fp64) -> status 1,
+ * converged_at = k, no move;  n_pos < 0 -> n_pos = 0, c_v = 1, c_f = 0;  P > 0 -> c_v = 1 - alpha, c_f = alpha sqrt(vv / ff)
+ * with the OLD alpha, then, if n_pos > n_min, dt = min(dt f_inc, dt_max) and alpha *= f_alpha, then n_pos += 1;  else
+ * c_v = c_f = 0, alpha = alpha_start, dt *= f_dec, n_pos = 0.  coef fp32 [n_mol, 4] = {c_v, c_f, dt, active (1 or 0)}, every
+ * number formed in fp64 and rounded once. */
+int gn_fire_plan(const float* force, const float* vel, const unsigned char* fixed, const int* mol_ptr, int N, int n_mol,
+                 double fmax, double dt_max, int n_min, double f_inc, double f_dec, double alpha_start, double f_alpha,
+                 float* dt, float* alpha, int* n_pos, int* status, int* converged_at, float* coef,
+                 const float* energy_keep, float* log, int log_len, const int* state, void* stream);
+/* The move of the molecules with coef[m][3] != 0: per free component vel = fmaf(dt, f, fmaf(c_f, f, c_v * vel)) in fp32; the
+ * squared length of the displacement sum (dt vel)^2 over the molecule in fp64; scale = fp32(min(1, max_step / length));
+ * pos += scale * (dt * vel) in fp32.  The clamp acts on the displacement of the whole molecule, not on the velocity. */
+int gn_fire_move(float* pos, float* vel, const float* force, const unsigned char* fixed, const int* mol_ptr, int N,
+                 int n_mol, const float* coef, double max_step, const int* state, void* stream);
+/* End of a step (one workgroup): state[1] += 1, and force [N, 3] / energy [n_mol] / stress [n_mol, 9] (NULL: none) are
+ * copied into their *_keep buffers for the molecules whose status is 0 (batch int64 [N], entries clamped to [0, n_mol)): a
+ * frozen molecule keeps the values it was judged on. */
+int gn_fire_finish(int* state, const int* status, const int64_t* batch, const float* force, float* force_keep, int N,
+                   const float* energy, float* energy_keep, const float* stress, float* stress_keep, int n_mol,
+                   void* stream);
+
 /* ---- parameter gradients (first-order training: a loss on energies and / or (h, X)) -------------
  * Every reduction below runs in a fixed order and uses no atomics: identical inputs give identical bits. */
 /* dW = dY^T A and db = sum_r dY of a Dense product y = A W^T + b (layers.py:457-529): several independent problems in
