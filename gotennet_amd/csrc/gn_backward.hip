@@ -1353,8 +1353,17 @@ static int message_backward(
     hipStream_t st = (hipStream_t)stream;
     // (F > 256: the degree-sliced kernels; g_rl / g_cut come as F / 256 partial slices, the caller sized them so)
     if (gn_use_highl(lmax_arg) || F > 256 || act != GN_ACT_SILU) return gn_highl_message_backward(p, lmax, sep_dir, sep_tensor, st);
-    const bool groups = X_in && gn_message_backward_groups(lmax_arg, sep_dir, sep_tensor, act) > 1;
+    const int G = gn_message_backward_groups(lmax_arg, sep_dir, sep_tensor, act);
+    const bool groups = X_in && G > 1;
     if (groups && (ga_parts == nullptr || E <= 0)) return GN_ERR_BAD_ARG;
+    if (groups && H > 8) {
+        // the degree-group kernels carry eight head sums per edge (msg_bwd_merged_group_body: vals[XR + 0..7]); with more
+        // heads the sums of heads 8 .. H - 1 were never formed and attn_bwd_kernel read unwritten workspace.  More than
+        // eight heads take the degree-sliced kernels, which write ONE g_cut slice: the other G - 1 the caller adds are zeroed
+        hipError_t err = hipMemsetAsync(g_cut + E, 0, (size_t)(G - 1) * (size_t)E * sizeof(float), st);
+        if (err != hipSuccess) return (int)err;
+        return gn_highl_message_backward(p, lmax, sep_dir, sep_tensor, st);
+    }
     if (F == 256) message_backward_launch<256>(p, lmax, sep_dir, sep_tensor, groups, ga_parts, E, st);
     else message_backward_launch<0>(p, lmax, sep_dir, sep_tensor, groups, ga_parts, E, st);
     GN_LAUNCH_CHECK();

@@ -361,6 +361,9 @@ int gn_message_backward_dropout(const float* x, const float* v, int ldxv, const 
  * ga_parts = NULL keeps the by-target / by-source pair (t_filter read by both).  The same holds for X_in == NULL (the first
  * interaction) at every lmax <= 4: with ga_parts ([E,H] floats) the single-read kernel runs in its form without the tensor-gate
  * blocks, without it the zero-X_in forms of the pair.  Same gradients either way (summation order aside).
+ * More than eight heads (H > 8) with G > 1: the degree-group kernels carry eight head sums per edge, so the call runs the
+ * degree-sliced kernels instead; they write ONE g_cut slice and the launcher zeroes the other G - 1, the caller's sizes
+ * and its sum over G slices stay as they are.
  * GN_LMAX_MAX in `lmax` (the reference's aggr = "max", gotennet.py:638-639): ga_parts is instead a workspace of
  * E x (1 + D) x F floats -- the upstream gradient of every per-edge MESSAGE, routed to the arg-max edge(s) of each output
  * element (evenly among exact ties, as torch's amax) before the degree-sliced backward kernels run; G = 1, X_in required. */
