@@ -48,6 +48,9 @@ SIGNATURES = {
     "gn_molecule_ptr": [_P, _I, _I, _P, _P],
     "gn_cosine_cutoff": [_P, _I, _F, _P, _P],
     "gn_out_degree": [_P, _I, _P, _P],
+    "gn_degree_scan": [_P, _I, _P, _P, _P],
+    "gn_padded_tail": [_P, _I, _I, C.c_int64, _P, _P, _P, _P, _P, _P],
+    "gn_graph_refresh": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "gn_edge_geometry": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P],
     "gn_node_init": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P],
     "gn_edge_init": [_P, _P, _P, _P, _I, _I, _I, _P, _P],

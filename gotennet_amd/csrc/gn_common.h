@@ -30,6 +30,24 @@ __device__ __forceinline__ bool self_loop(int j, int i, const float* __restrict_
     return j == i && (loop_dist == nullptr || loop_dist[e] == 0.0f);
 }
 
+// Edge e (< E, E > 0) of a target-sorted int64 [2, E] list: its int32 copies and the CSR row pointers it owns -- the rows
+// after the previous edge's target up to its own, and the rest up to N for the last edge.  The body of gn_build_csr and of
+// gn_graph_refresh's first launch: one definition.  Targets outside [0, N) -- a caller error gn_check_edges reports -- are
+// clamped: nothing is written out of bounds.
+__device__ __forceinline__ void csr_split_edge(const int64_t* __restrict__ ei, int e, int E, int N, int* __restrict__ src,
+                                               int* __restrict__ dst, int* __restrict__ rowptr) {
+    const int s = (int)ei[e];
+    const int d = (int)ei[(size_t)E + e];
+    src[e] = s;
+    dst[e] = d;
+    const int dc = d < 0 ? -1 : (d >= N ? N - 1 : d);
+    int prev = e > 0 ? (int)ei[(size_t)E + e - 1] : -1;
+    prev = prev < -1 ? -1 : (prev >= N ? N - 1 : prev);
+    for (int n = prev + 1; n <= dc; ++n) rowptr[n] = e;
+    if (e == E - 1)
+        for (int n = dc + 1; n <= N; ++n) rowptr[n] = E;
+}
+
 // sigmoid on the hardware transcendentals: v_exp_f32 (2^x) and v_rcp_f32, ~1 ulp each -- 4 VALU instead of the ~20 of
 // expf + an IEEE division.  Round-3 counters: the segment softmax was VALU-bound (1080 VALU instructions per wave, 23 of
 // its 29 us), SiLU / SiLU' are a quarter of the VALU work of the HTR and message backward passes.  Error: the argument

@@ -22,17 +22,7 @@ __global__ void build_csr_kernel(const int64_t* __restrict__ ei, int E, int N,
         return;
     }
     if (e >= E) return;
-    const int s = (int)ei[e];
-    const int d = (int)ei[(size_t)E + e];
-    src[e] = s;
-    dst[e] = d;
-    // (targets outside [0, N) -- a caller error gn_check_edges reports -- must not make this kernel write out of bounds)
-    const int dc = d < 0 ? -1 : (d >= N ? N - 1 : d);
-    int prev = e > 0 ? (int)ei[(size_t)E + e - 1] : -1;
-    prev = prev < -1 ? -1 : (prev >= N ? N - 1 : prev);
-    for (int n = prev + 1; n <= dc; ++n) rowptr[n] = e;
-    if (e == E - 1)
-        for (int n = dc + 1; n <= N; ++n) rowptr[n] = E;
+    csr_split_edge(ei, e, E, N, src, dst, rowptr);
 }
 
 // CosineCutoff (layers.py:149-152) of a distance vector -- for callers that drive one GATA layer directly

@@ -180,10 +180,12 @@ __global__ void csc_count_kernel(const int* __restrict__ src, int E, int* __rest
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < E) atomicAdd(cnt + src[e], 1);
 }
-// one workgroup: colptr = exclusive scan of cnt (N + 1 entries), cursor = a copy of colptr[0..N) for the scatter.
-// `cursor` MAY alias `cnt` (the launcher scans in place: a thread reads cnt[n] before it writes cursor[n], and no other
-// thread touches entry n) -- neither pointer is __restrict__
-__global__ __launch_bounds__(1024) void csc_scan_kernel(const int* cnt, int N, int* __restrict__ colptr, int* cursor) {
+// One workgroup of 1024 threads: the exclusive scan of v[0 .. N), handed to write(n, sum of v[0 .. n)) by the thread that read
+// v[n]; returns the total (to every thread).  Inclusive scan inside each wave, the waves' sums through LDS, a carry across
+// trips of 1024 entries.  A thread reads v[n] before it calls write(n, .) and no other thread touches entry n: `write` may
+// store over v itself.  The one scan of this file: csc_scan_kernel and degree_scan_kernel are its two callers.
+template <class Write>
+__device__ __forceinline__ int block_exclusive_scan(const int* v_in, int N, Write write) {
     __shared__ int part[16];
     __shared__ int carry;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -191,7 +193,7 @@ __global__ __launch_bounds__(1024) void csc_scan_kernel(const int* cnt, int N, i
     __syncthreads();
     for (int base = 0; base < N; base += 1024) {
         const int n = base + t;
-        const int v = n < N ? cnt[n] : 0;
+        const int v = n < N ? v_in[n] : 0;
         int incl = v;                                            // inclusive scan inside the wave
         for (int o = 1; o < 64; o <<= 1) {
             const int u = __shfl_up(incl, o, 64);
@@ -201,15 +203,31 @@ __global__ __launch_bounds__(1024) void csc_scan_kernel(const int* cnt, int N, i
         __syncthreads();
         int before = carry;
         for (int w = 0; w < wave; ++w) before += part[w];
-        if (n < N) {
-            colptr[n] = before + incl - v;
-            cursor[n] = before + incl - v;
-        }
+        if (n < N) write(n, before + incl - v);
         __syncthreads();
         if (t == 1023) carry = before + incl;
         __syncthreads();
     }
-    if (t == 0) colptr[N] = carry;
+    return carry;
+}
+// one workgroup: colptr = exclusive scan of cnt (N + 1 entries), cursor = a copy of colptr[0..N) for the scatter.
+// `cursor` MAY alias `cnt` (the launcher scans in place) -- neither pointer is __restrict__
+__global__ __launch_bounds__(1024) void csc_scan_kernel(const int* cnt, int N, int* __restrict__ colptr, int* cursor) {
+    const int total = block_exclusive_scan(cnt, N, [=](int n, int s) {
+        colptr[n] = s;
+        cursor[n] = s;
+    });
+    if (threadIdx.x == 0) colptr[N] = total;
+}
+// gn_degree_scan: rowptr64 = the exclusive scan of the searches' deg (N + 1 entries, int64: what FillSink reads), the total
+// also into the device word n_edges -- what torch.cumsum and a host read of its last entry give graph.distance*
+__global__ __launch_bounds__(1024) void degree_scan_kernel(const int* __restrict__ deg, int N, int64_t* __restrict__ rowptr64,
+                                                           int* __restrict__ n_edges) {
+    const int total = block_exclusive_scan(deg, N, [=](int n, int s) { rowptr64[n] = s; });
+    if (threadIdx.x == 0) {
+        rowptr64[N] = total;
+        n_edges[0] = total;
+    }
 }
 __global__ void csc_scatter_kernel(const int* __restrict__ src, int E, int* __restrict__ cursor, int* __restrict__ tmp) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -255,6 +273,47 @@ __global__ __launch_bounds__(256) void csc_rank_kernel(const int* __restrict__ c
             tgt_by_src[p0 + r] = dst[id];
         }
     }
+}
+
+// gn_graph_refresh's first launch: what gn_build_csr writes (csr_split_edge: the same body), and the zeroes that
+// gn_build_csc's memset and gn_out_degree's caller supply -- in a kernel, so a recorded chain holds kernel nodes only.
+// Grid over max(E, N + 1).
+__global__ void refresh_split_kernel(const int64_t* __restrict__ ei, int E, int N, int* __restrict__ src, int* __restrict__ dst,
+                                     int* __restrict__ rowptr, int* __restrict__ cnt, int* __restrict__ outdeg) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < N) {
+        cnt[t] = 0;
+        if (outdeg != nullptr) outdeg[t] = 0;
+    }
+    if (E == 0) {
+        if (t <= N) rowptr[t] = 0;
+        return;
+    }
+    if (t < E) csr_split_edge(ei, t, E, N, src, dst, rowptr);
+}
+
+// gn_padded_tail: the slots [E_real, capacity) of a [2, capacity] list, E_real = rowptr64[N] read HERE, as self-loops of the
+// dummy atoms N .. N + n_pad - 1 (shift, vector and distance 0), dealt in the balanced contiguous partition of
+// graph.PaddedLayout.tail_degrees: P = capacity - E_real slots, the first P % n_pad dummies get P / n_pad + 1, the others
+// P / n_pad.  One thread per tail slot t = slot - E_real; its dummy is closed-form: with q = P / n_pad, r = P % n_pad the
+// first r (q + 1) slots belong to t / (q + 1), the rest to r + (t - r (q + 1)) / q  (q >= 1 because P >= n_pad).
+// E_real outside [N, capacity - n_pad] -- a count the layout's bound excludes -- writes nothing and sets the sticky word.
+template <bool SHIFTS>
+__global__ void padded_tail_kernel(const int64_t* __restrict__ rowptr64, int N, int n_pad, int64_t capacity,
+                                   int64_t* __restrict__ edge_index, int* __restrict__ edge_shift, float* __restrict__ edge_vec,
+                                   float* __restrict__ edge_diff, int* __restrict__ state) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t E_real = rowptr64[N];
+    if (E_real < N || E_real > capacity - n_pad) {
+        if (t == 0) state[0] = 1;
+        return;
+    }
+    const int64_t P = capacity - E_real;
+    if (t >= P) return;
+    const int64_t q = P / n_pad, r = P % n_pad, head = r * (q + 1);
+    const int k = N + (int)(t < head ? t / (q + 1) : r + (t - head) / q);
+    store_edge<true, SHIFTS>(E_real + t, capacity, k, k, Image{0.f, 0.f, 0.f, 0.f, 0, 0, 0}, edge_index, edge_shift, edge_vec,
+                             edge_diff);
 }
 
 // offsets of the molecules in a SORTED batch vector: mol_ptr[m] = first atom with batch >= m  (m = 0 .. n_mol).
@@ -444,6 +503,53 @@ extern "C" int gn_build_csc(const int* src, const int* dst, int E, int N, int* c
     if (E > 0) {
         hipLaunchKernelGGL(gn::csc_scatter_kernel, dim3((E + 255) / 256), dim3(256), 0, st, src, E, cnt, tmp);
         hipLaunchKernelGGL(gn::csc_rank_kernel, dim3((N + 3) / 4), dim3(256), 0, st, colptr, tmp, dst, N, perm, tgt_by_src);
+    }
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+/* ---- a neighbour list rebuilt inside a recorded step: kernel launches only, no memset, no copy, no host read ----------- */
+extern "C" int gn_degree_scan(const int* deg, int N, int64_t* rowptr64, int* n_edges, void* stream) {
+    if (N < 0 || !rowptr64 || !n_edges || (N > 0 && !deg)) return GN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(gn::degree_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, deg, N, rowptr64, n_edges);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_padded_tail(const int64_t* rowptr64, int N, int n_pad, int64_t capacity, int64_t* edge_index,
+                              int* edge_shift, float* edge_vec, float* edge_diff, int* state, void* stream) {
+    if (N < 0 || n_pad < 1 || capacity < (int64_t)N + n_pad || capacity > 0x7fffffff) return GN_ERR_BAD_ARG;
+    if (!rowptr64 || !edge_index || !edge_vec || !edge_diff || !state) return GN_ERR_BAD_ARG;
+    const dim3 grid((unsigned)((capacity - N + 255) / 256)), block(256);          // the longest tail: self-loops only
+    if (edge_shift)
+        hipLaunchKernelGGL(gn::padded_tail_kernel<true>, grid, block, 0, (hipStream_t)stream, rowptr64, N, n_pad, capacity,
+                           edge_index, edge_shift, edge_vec, edge_diff, state);
+    else
+        hipLaunchKernelGGL(gn::padded_tail_kernel<false>, grid, block, 0, (hipStream_t)stream, rowptr64, N, n_pad, capacity,
+                           edge_index, edge_shift, edge_vec, edge_diff, state);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_graph_refresh(const int64_t* edge_index, int E, int N, int* src, int* dst, int* rowptr, int* outdeg,
+                                int* colptr, int* perm, int* tgt_by_src, int* work, void* stream) {
+    if (E < 0 || N < 0 || !rowptr || !colptr || (N > 0 && !work)) return GN_ERR_BAD_ARG;
+    if (E > 0 && (!edge_index || !src || !dst || !perm || !tgt_by_src || !work)) return GN_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int* cnt = work;                                             // gn_build_csc's layout: [N] counts, then [E] bucket contents
+    int* tmp = work + N;
+    const int items = E > N + 1 ? E : N + 1;
+    const dim3 edges((E + 255) / 256), block(256);
+    hipLaunchKernelGGL(gn::refresh_split_kernel, dim3((items + 255) / 256), block, 0, st, edge_index, E, N, src, dst, rowptr,
+                       cnt, outdeg);
+    if (E > 0) {
+        hipLaunchKernelGGL(gn::csc_count_kernel, edges, block, 0, st, src, E, cnt);
+        if (outdeg) hipLaunchKernelGGL(gn::csc_count_kernel, edges, block, 0, st, src, E, outdeg);   // (gn_out_degree's count)
+    }
+    hipLaunchKernelGGL(gn::csc_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, N, colptr, cnt);
+    if (E > 0) {
+        hipLaunchKernelGGL(gn::csc_scatter_kernel, edges, block, 0, st, src, E, cnt, tmp);
+        hipLaunchKernelGGL(gn::csc_rank_kernel, dim3((N + 3) / 4), block, 0, st, colptr, tmp, dst, N, perm, tgt_by_src);
     }
     GN_LAUNCH_CHECK();
     return GN_OK;

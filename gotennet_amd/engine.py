@@ -386,7 +386,7 @@ class Graph:
         self.rl = torch.empty((E, cfg.D), **f32)
         self.phi = torch.empty((E, max(cfg.R, 0)), **f32)
         self.cut = torch.empty(E, **f32)
-        self.perm = self.colptr = self.tgt_by_src = None
+        self.perm = self.colptr = self.tgt_by_src = self._work = None      # (_work: ``refresh``'s scratch)
         self.edge_diff = self.edge_vec = None
         #: periodic list (graph.distance_pbc): int32 [E, 3] lattice shifts, the int64 batch vector and the fp32 [n_mol, 3, 3]
         #: cell (``set_periodic``); None for an isolated-molecule list
@@ -445,6 +445,23 @@ class Graph:
             call("gn_build_csc", ptr(self.src), ptr(self.dst), self.E, self.N, ptr(self.colptr), ptr(self.perm),
                  ptr(self.tgt_by_src), ptr(work), _stream())
         return self.colptr, self.perm
+
+    def refresh(self, edge_index: torch.Tensor):
+        """Re-derive the topology IN PLACE from a new target-major ``edge_index`` of the same shape (gn_graph_refresh: what the
+        constructor and ``csc()`` compute, into the buffers that exist; kernel launches only, no allocation after the first
+        call, no host sync).  For a list of fixed capacity that is rebuilt on the device (``graph.rebuild_padded``); the geometry
+        is the caller's next ``set_geometry``."""
+        if (tuple(edge_index.shape) != (2, self.E) or edge_index.dtype != torch.int64 or not edge_index.is_contiguous()
+                or edge_index.device != self.src.device):
+            raise ValueError(f"refresh: a contiguous int64 [2, {self.E}] edge_index on the graph's device is expected")
+        if self.perm is None or self._work is None:
+            i32 = dict(dtype=torch.int32, device=self.src.device)
+            self.colptr, self.perm = torch.empty(self.N + 1, **i32), torch.empty(self.E, **i32)
+            self.tgt_by_src = torch.empty(self.E, **i32)
+            self._work = torch.empty(self.N + self.E, **i32)
+        call("gn_graph_refresh", ptr(edge_index), self.E, self.N, ptr(self.src), ptr(self.dst), ptr(self.rowptr),
+             ptr(self.outdeg), ptr(self.colptr), ptr(self.perm), ptr(self.tgt_by_src), ptr(self._work), _stream())
+        return self
 
 
 @dataclass

@@ -6,7 +6,9 @@ per-target degrees and the read-back of the edge count needed to size the
 outputs (one sync, as in torch_cluster).
 
 ``PaddedLayout`` is host-side index arithmetic only: the fixed sizes a radius graph needs
-to be rebuilt on the device without that read-back (no kernel consumes it yet)."""
+to be rebuilt on the device without that read-back.  ``rebuild_padded`` is that rebuild: the
+searches' own count and fill kernels around a device scan, then the inert tail
+(``pipeline.RebuiltStep`` records it in front of the model)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -273,8 +275,8 @@ def list_is_current(pos: torch.Tensor, batch: torch.Tensor, edge_index: torch.Te
 
 class PaddedLayout:
     """Fixed sizes for a radius graph that is rebuilt on the device -- an MD step recorded into one hipGraph whose neighbour
-    list changes (host work, once per trajectory: the molecule sizes are read here).  The layout only; the kernels that
-    fill such a list are not part of the library yet.
+    list changes (host work, once per trajectory: the molecule sizes are read here).  The layout only; ``rebuild_padded``
+    launches the kernels that fill such a list.
 
     ``e_bound`` = sum_m n_m * min(n_m, max_num_neighbors) bounds the edge count of ANY positions (gn_radius_count counts
     the self-loop inside the cap), so an edge list of that capacity cannot overflow.  The slots a step does not use must
@@ -285,14 +287,20 @@ class PaddedLayout:
     row holds between 1 and ``pad_degree`` + 1 edges.  No edge joins a dummy atom to a real one: real rows see what they see
     in the unpadded graph.
 
+    ``periodic_images=True``: the list comes from a multi-image search (``distance_pbc(images="all")``), where one pair can
+    contribute several edges and an atom sees its own images, so a molecule of n atoms fills every row up to the cap
+    whatever n is: ``e_bound`` = sum_m n_m * max_num_neighbors.  Open and minimum-image lists hold one edge per pair and keep
+    the bound above.
+
     Provides ``batch`` (int64 [n_atoms]) and ``mol_ptr`` (int32 [n_mol + 2]) of the padded system, and ``z`` (int32
     [n_atoms]) when the atomic numbers are passed (``pad_z`` otherwise): call the engine with ``n_mol + 1`` molecules and
     keep ``energy[:n_mol]``, ``forces[:N]``."""
 
     def __init__(self, batch: torch.Tensor, n_mol: int, max_num_neighbors: int = 32, pad_degree: Optional[int] = None,
-                 z: Optional[torch.Tensor] = None):
+                 z: Optional[torch.Tensor] = None, periodic_images: bool = False):
         from .outputs import molecule_ptr
         self.n_mol, self.max_num_neighbors = int(n_mol), int(max_num_neighbors)
+        self.periodic_images = bool(periodic_images)
         self.pad_degree = int(pad_degree) if pad_degree is not None else self.max_num_neighbors
         if self.n_mol < 1 or self.max_num_neighbors < 1 or self.pad_degree < 1:
             raise ValueError("PaddedLayout needs n_mol, max_num_neighbors and pad_degree >= 1")
@@ -302,7 +310,8 @@ class PaddedLayout:
         if N == 0 or int(b.min()) < 0 or int(b.max()) >= self.n_mol or bool((b[1:] < b[:-1]).any()):
             raise ValueError("batch must be non-empty, non-decreasing and hold molecule indices in [0, n_mol)")
         self.sizes = torch.bincount(b, minlength=self.n_mol).tolist()
-        self.e_bound = sum(n * min(n, self.max_num_neighbors) for n in self.sizes)
+        self.e_bound = sum(n * (self.max_num_neighbors if self.periodic_images else min(n, self.max_num_neighbors))
+                           for n in self.sizes)
         self.n_pad = max(1, -(-(self.e_bound - N) // self.pad_degree))
         self.edge_capacity = self.e_bound + self.n_pad
         self.n_atoms = N + self.n_pad
@@ -330,3 +339,29 @@ class PaddedLayout:
             raise ValueError(f"{n_edges} edges: outside [{self.N}, {self.e_bound}]")
         base, rem = divmod(P, self.n_pad)
         return [base + (1 if k < rem else 0) for k in range(self.n_pad)]
+
+
+def rebuild_padded(pos, batch, mol_ptr, n_mol: int, cutoff: float, max_num_neighbors: int, n_pad: int, deg, rowptr64,
+                   edge_count, edge_index, edge_shift, edge_vec, edge_diff, state, cell=None, inv_cell=None,
+                   image_range=None) -> None:
+    """The radius graph of the N real atoms ``pos`` into a list of fixed capacity (``PaddedLayout``: ``edge_index`` int64
+    [2, capacity], ``edge_shift`` int32 [capacity, 3] or None, ``edge_vec`` [capacity, 3], ``edge_diff`` [capacity]), on prepared
+    device arrays: count -> gn_degree_scan -> fill with E = capacity -> gn_padded_tail.  Four kernel launches, no allocation,
+    no memset and no host read -- what a recorded step launches.  Columns [0, E_real) are ``distance`` / ``distance_pbc``'s, bit
+    for bit (the same walk, the same sinks); E_real lands in ``edge_count`` int32 [1]; the tail belongs to the dummy atoms
+    N .. N + n_pad - 1.  ``deg`` int32 [N] and ``rowptr64`` int64 [N + 1] are scratch; ``state[0]`` is set when the count leaves
+    the layout's bound.  ``cell`` None: the open search; ``image_range`` None: the minimum-image search; else the multi-image one."""
+    N, capacity = pos.shape[0], edge_index.shape[1]
+    st = torch.cuda.current_stream().cuda_stream
+    if cell is None:
+        entry, search, outs = "", (ptr(pos), ptr(batch), N, float(cutoff), int(max_num_neighbors)), (ptr(edge_index),)
+    else:
+        box = (ptr(cell), ptr(inv_cell)) if image_range is None else (ptr(cell), ptr(inv_cell), ptr(image_range))
+        entry = "_pbc" if image_range is None else "_pbc_images"
+        search = (ptr(pos), ptr(batch), ptr(mol_ptr), *box, N, n_mol, float(cutoff), int(max_num_neighbors))
+        outs = (ptr(edge_index), ptr(edge_shift))
+    call("gn_radius_count" + entry, *search, ptr(deg), st)
+    call("gn_degree_scan", ptr(deg), N, ptr(rowptr64), ptr(edge_count), st)
+    call("gn_radius_fill" + entry, *search, ptr(rowptr64), capacity, *outs, ptr(edge_vec), ptr(edge_diff), st)
+    call("gn_padded_tail", ptr(rowptr64), N, int(n_pad), capacity, ptr(edge_index), ptr(edge_shift) if cell is not None else None,
+         ptr(edge_vec), ptr(edge_diff), ptr(state), st)

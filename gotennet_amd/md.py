@@ -16,6 +16,13 @@ positions, records a new graph, finishes the interrupted step eagerly with the s
 reference of the captured mode -- the two trajectories agree bit for bit -- and the better choice for systems whose list
 changes in almost every step.
 
+``rebuild="device"`` (opt-in; ``rebuild="host"``, the default, is the paragraph above) replaces "neighbour list" by the REBUILD of
+the list inside the step: the search's own count and fill kernels around a device scan, into a list of fixed capacity whose
+unused tail belongs to dummy atoms (``pipeline.RebuiltStep``, ``graph.PaddedLayout``).  The list is never stale, so there is no
+verify kernel, no repair and no second recording; the sticky word is set only by the overflow guard of gn_padded_tail, and the
+host reads the state every ``check_every`` replays for the step counter.  ``captured=False`` launches the same chain eagerly on
+the same padded buffers.  The cell is fixed in this mode.
+
 Constant pressure (``barostat=``): isotropic stochastic cell rescaling (Bernetti and Bussi, J. Chem. Phys. 153, 114107, 2020)
 written in eps = ln V.  Per box and step::
 
@@ -52,7 +59,7 @@ import torch
 from . import engine, graph
 from ._lib import call, ptr
 from .outputs import _ATOMIC_MASS, molecule_ptr
-from .pipeline import CapturedStep, EnergyForces
+from .pipeline import CapturedStep, EnergyForces, RebuiltStep
 
 #: ``force_scale`` turns force / mass into an acceleration in the caller's length and time units:
 #: a = force_scale * F / m.  1 when the units are consistent already (the default).  Two common sets, masses in amu,
@@ -118,10 +125,24 @@ def barostat_parameters(barostat: dict, thermostat: Optional[dict], cell) -> dic
     return out
 
 
+REBUILD_MODES = ("host", "device")
+
+
+def check_rebuild(rebuild, barostat=None) -> None:
+    """``rebuild=`` of ``MDRun`` / ``relax.Relax``, or ``ValueError``: a known mode, and no barostat in device mode (a moving cell
+    can outgrow the image ranges of the search, which is a host decision)."""
+    if rebuild not in REBUILD_MODES:
+        raise ValueError(f"rebuild must be one of {REBUILD_MODES}, got {rebuild!r}")
+    if rebuild == "device" and barostat is not None:
+        raise ValueError('rebuild="device" with a barostat: the device rebuild runs on a fixed cell (a moving cell can outgrow '
+                         'the image ranges, which the host decides); use rebuild="host"')
+
+
 def validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images="minimum", check_every=1, log_len=1,
-             barostat=None):
+             rebuild="host", barostat=None):
     """Everything ``MDRun`` refuses, before any launch -> (mass table fp32 on the CPU, ``graph.resolve_images``' result or None).
     Raises ``ValueError``.  Reads ``z`` (and ``cell``) on the host."""
+    check_rebuild(rebuild, barostat)
     if not (math.isfinite(float(dt)) and float(dt) > 0):
         raise ValueError(f"dt must be positive and finite, got {dt}")
     if not (math.isfinite(float(force_scale)) and float(force_scale) > 0):
@@ -189,6 +210,23 @@ class _RecordedStep(CapturedStep):
         return out
 
 
+class _RebuiltRecordedStep(RebuiltStep):
+    """``rebuild="device"``: ``RebuiltStep`` with the integrator around its body -- ``_pre`` -> the rebuild -> model -> ``_post`` --
+    recorded (``capture``) or launched eagerly on the same padded buffers.  No verify kernel: the list is never stale.  The
+    driver's sticky word is the one gn_padded_tail sets; the driver is held weakly, as in ``_RecordedStep``."""
+
+    def __init__(self, md: "_ListDriver", capture: bool):
+        self.md = weakref.proxy(md)
+        super().__init__(md.ef, md._z, md._batch, md.n_mol, max_num_neighbors=md.max_num_neighbors, cell=md._cell,
+                         images=md.images, capture=capture, state=md._state)
+
+    def _body(self):
+        self.md._pre(self.pos, self.cell)
+        out = super()._body()
+        self.md._post(*out)
+        return out
+
+
 class _EagerStep:
     """What ``CapturedStep._body`` reads, for a list that is rebuilt in every step: the same body, launched eagerly."""
     _body = CapturedStep._body
@@ -208,7 +246,20 @@ class _EagerStep:
         self.g.csc()
 
 
-class _ListDriver:
+class _RebuildOption(type):
+    """The constructor call of a driver takes ``rebuild="host" | "device"`` next to the arguments of its ``__init__``, whose
+    parameter lists are a pinned public surface and stay what they were.  The mode is checked and stored on the instance
+    (``self.rebuild``) before ``__init__`` runs, so everything ``__init__`` refuses it still refuses before any launch."""
+
+    def __call__(cls, *args, rebuild: str = "host", **kw):
+        check_rebuild(rebuild)
+        self = cls.__new__(cls)
+        self.rebuild = rebuild
+        self.__init__(*args, **kw)
+        return self
+
+
+class _ListDriver(metaclass=_RebuildOption):
     """What ``MDRun`` and ``relax.Relax`` share, once: the neighbour search, the device check of the stored list, the
     record / repair / replay loop and the handling of the sticky word.  A driver supplies ``_pre(pos, cell)`` (everything before
     the neighbour list) and ``_post(energy, forces[, stress])`` (everything after the model) -- the protocol ``_RecordedStep`` and
@@ -234,6 +285,16 @@ class _ListDriver:
 
     def _start(self, start):
         """The first list and the first model evaluation at ``start`` -> (energy, forces[, stress]) of the step's own buffers."""
+        if self.rebuild == "device":
+            # the step owns the padded buffers; recorded or not, the chain is the same.  The sticky word is held at 1 while
+            # the recording's warm-up runs (they advance nothing), as in ``_record``
+            self._state[:1].fill_(1)
+            self._step = _RebuiltRecordedStep(self, capture=self.captured)
+            self._step.pos.copy_(start)
+            self._pos, self._cell, self._fresh = self._step.pos, self._step.cell, self.captured
+            self._state[:1].zero_()
+            with torch.no_grad():
+                return self._step.model()
         lst = self._list(start)
         if self.captured:
             self._step, self._pos = None, start
@@ -296,6 +357,8 @@ class _ListDriver:
     def run(self, n: int):
         """Advance ``n`` steps.  Captured: the host reads the device state after every ``check_every`` replays, after the first
         replay of a newly recorded graph and at the end (a stream synchronisation each)."""
+        if self.rebuild == "device":
+            return self._run_device(int(n))
         if not self.captured:
             for _ in range(int(n)):
                 self._pre(self._pos, self._cell)
@@ -324,6 +387,34 @@ class _ListDriver:
                 break
         return self
 
+    def _run_device(self, n: int):
+        """``rebuild="device"``: nothing is verified, repaired or re-recorded.  The host reads the device state after every
+        ``check_every`` steps (after the first replay of the graph, and at the end) for the step counter, ``_looked`` and the
+        overflow guard of gn_padded_tail only."""
+        target = self._done + n
+        while self._done < target:
+            burst = 1 if self._fresh else min(self.check_every, target - self._done)
+            for _ in range(burst):
+                if self.captured:
+                    self._step.graph.replay()
+                else:
+                    self._step._body()
+            self._fresh = False
+            overflow, self._done = self._state.tolist()          # (the synchronisation)
+            if overflow:
+                raise RuntimeError(f"the neighbour search found {self.edge_count} edges, outside the padded layout's bound "
+                                   f"[{self.N}, {self._step.layout.e_bound}]: the run stops at step {self._done}")
+            if self._looked():
+                break
+        return self
+
+    @property
+    def edge_count(self) -> int:
+        """The real edges of the current neighbour list (device mode: one host read of the device word)."""
+        if self.rebuild == "device":
+            return int(self._step.edge_count.item())
+        return self._step.g.E if self.captured else self._lst[0].shape[1]
+
     def _ring(self, log):
         k = min(self.step, self.log_len)
         rows = [(s % self.log_len) for s in range(self.step - k, self.step)]
@@ -347,6 +438,14 @@ class MDRun(_ListDriver):
     the stale-list word (the trajectory does not depend on it).  ``log_len``: rows of the (potential, kinetic) energy ring
     buffer.  ``captured=False``: the eager reference (module docstring).
 
+    ``rebuild`` (a keyword of the constructor call, ``MDRun(..., rebuild="device")``, taken by the drivers' metaclass; not a
+    parameter of ``__init__``): "host" (default: the modes of the module docstring) or "device": the list is REBUILT inside every step by the
+    search's own kernels into a list of fixed capacity (``pipeline.RebuiltStep``) -- no verify kernel, no repair, no second
+    recording; ``rebuilds`` stays 0 and ``edge_count`` reports the current number of real edges.  For systems whose list changes
+    often (a host rebuild costs about ten eager steps).  ``captured=False, rebuild="device"`` launches the same chain eagerly on
+    the same padded buffers and agrees with the recorded one bit for bit; in the "f32" and "split" arithmetics both are the
+    ``rebuild="host"`` trajectory, bit for bit.  The cell is fixed: ``barostat=`` is refused in this mode.
+
     ``barostat``: None (the cell is fixed: the launches and the bits of a run without this argument) or
     ``dict(pressure=, tau=, compressibility=, kT=None, key=None, max_step=0.05)``: isotropic stochastic cell rescaling on the
     device, inside the replay (module docstring: the scheme, its placement -- a first-order splitting, the driving pressure lags
@@ -360,7 +459,8 @@ class MDRun(_ListDriver):
 
     Refused with ``ValueError`` before any launch: dt <= 0, a negative or missing mass, kT < 0, gamma < 0, a cell that
     ``graph.resolve_images`` refuses, ``pos`` or ``cell`` requiring grad; a barostat without a cell, with entries missing, with
-    tau, compressibility or max_step not positive and finite, a non-finite pressure, kT < 0, or kT > 0 without a key."""
+    tau, compressibility or max_step not positive and finite, a non-finite pressure, kT < 0, or kT > 0 without a key; an
+    unknown ``rebuild``, or ``rebuild="device"`` with a barostat."""
 
     def __init__(self, ef: EnergyForces, z: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, n_mol: int, dt: float,
                  masses=None, force_scale: float = 1.0, vel: Optional[torch.Tensor] = None,
@@ -368,7 +468,7 @@ class MDRun(_ListDriver):
                  thermostat: Optional[dict] = None, check_every: int = 1, log_len: int = 1024, captured: bool = True,
                  barostat: Optional[dict] = None):
         table, ranges = validate(z, pos, dt, masses, force_scale, thermostat, cell, float(ef.rep.cutoff), images, check_every,
-                                 log_len, barostat)
+                                 log_len, rebuild=self.rebuild, barostat=barostat)
         dev = pos.device
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
         self._setup(ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured)

@@ -415,3 +415,121 @@ class CapturedStep:
         if self.cell is None:
             return self.energy, self.forces
         return self.energy, self.forces, self.stress
+
+
+class RebuiltStep:
+    """Energy + forces with the neighbour list REBUILT inside the step: ``CapturedStep``'s counterpart for lists that change
+    (liquids, hot molecules), still ONE hipGraph replay per step and no host read.
+
+        step = RebuiltStep(EnergyForces(rep, head), z, batch, n_mol)             # or cell=, images= for periodic boxes
+        energy, forces = step(pos)          # views of static output buffers: copy them to keep them
+        step.edge_count                     # int32 [1] on the device: the real edges of the last step
+
+    The list gets a fixed capacity (``graph.PaddedLayout``): ``n_pad`` dummy atoms of atomic number 0 in one extra molecule own
+    the slots a step does not use, as self-loops with zero vector and distance.  The recorded chain is count (over the N real
+    atoms) -> gn_degree_scan -> fill (E = capacity) -> gn_padded_tail -> gn_graph_refresh -> [gn_cell_prepare] -> geometry ->
+    forward -> head -> backward -> force scatter -> [gn_virial]: kernel nodes only, on one stream.  The model runs on
+    N + n_pad atoms and n_mol + 1 molecules; what is returned are the first n_mol energies (and stresses) and the first N
+    forces.  No edge joins a dummy atom to a real one, so in the "f32" and "split" arithmetics these are the bits of
+    ``EnergyForces`` on the unpadded list; "f16x2" shares block exponents between neighbouring rows and agrees to its usual
+    1e-6 relative.  ``step.edge_index`` / ``step.edge_shift`` are the capacity-sized buffers.
+
+    Periodic steps (``cell``, ``images`` as ``graph.distance_pbc``): the cell is FIXED -- the image ranges of the search are a
+    host decision -- and a cell passed per call is refused.  The dummy molecule gets the identity cell (volume 1, zero virial);
+    ``step.cell`` is the [n_mol, 3, 3] view of the real boxes.
+
+    ``capture=False``: the same launches on the same buffers, eagerly in every call (the reference of the recorded mode).
+    ``state``: an int32 tensor whose first word gn_padded_tail sets when the edge count leaves the layout's bound (sticky;
+    default: the step's own).  An inference tool, like ``CapturedStep``."""
+
+    def __init__(self, ef: EnergyForces, z: torch.Tensor, batch: torch.Tensor, n_mol: int, max_num_neighbors: int = 32,
+                 cell: Optional[torch.Tensor] = None, images: str = "minimum", warmup: int = 2, capture: bool = True,
+                 state: Optional[torch.Tensor] = None):
+        rep, head = ef.rep, ef.head
+        if cell is not None and cell.requires_grad:          # before any launch
+            raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
+        if images not in graph.IMAGE_MODES:
+            raise ValueError(f"images must be one of {graph.IMAGE_MODES}, got {images!r}")
+        ranges = graph.resolve_images(cell, float(rep.cutoff), images) if cell is not None else None
+        dev = z.device
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        self.layout = lay = graph.PaddedLayout(batch, n_mol, max_num_neighbors, z=z, periodic_images=ranges is not None).to(dev)
+        self.cfg, self.pw, self.head = rep.config(), rep.packed_weights(), head
+        self.images, self.cutoff, self.max_num_neighbors = images, float(rep.cutoff), int(max_num_neighbors)
+        self.N, self.n_mol, self.n_pad, self.capacity = lay.N, int(n_mol), lay.n_pad, lay.edge_capacity
+        self.z32, self.mol_ptr = lay.z, lay.mol_ptr                      # the padded system: what the model runs on
+        self.batch = batch.to(device=dev, dtype=torch.int64).contiguous()  # the real atoms: what the search runs on
+        self._real_ptr = molecule_ptr(self.batch, self.n_mol)
+        # every buffer of the chain is made and initialised here, by torch, never inside the recording
+        self.pos = torch.zeros((self.N, 3), **f32)                      # static input buffer
+        self.state = torch.zeros(1, **i32) if state is None else state
+        self.edge_count = torch.zeros(1, **i32)
+        self._deg, self._rowptr64 = torch.zeros(self.N, **i32), torch.zeros(self.N + 1, dtype=torch.int64, device=dev)
+        self.edge_index = torch.zeros((2, self.capacity), dtype=torch.int64, device=dev)
+        self.edge_vec, self.edge_diff = torch.zeros((self.capacity, 3), **f32), torch.zeros(self.capacity, **f32)
+        self.edge_shift = self.cell = self._cell_all = self.inv_cell = self.volume = self._ranges = None
+        if cell is not None:
+            self.edge_shift = torch.zeros((self.capacity, 3), **i32)
+            self._cell_all = torch.cat([graph.broadcast_cell(cell.to(dev), self.n_mol), torch.eye(3, **f32).unsqueeze(0)])
+            self.cell = self._cell_all[:self.n_mol]                     # a view: the driver's [n_mol, 3, 3] cell
+            self.inv_cell, self.volume = graph.cell_prepare(self._cell_all)     # (the search reads the inverse before step 6)
+            self._ranges = None if ranges is None else ranges.expand(self.n_mol, 3).contiguous().to(dev)
+        self.g = engine.Graph(self.cfg, self.pw, lay.n_atoms, self.edge_index, self_images=cell is not None)
+        self.energy = self.forces = self.stress = self.graph = None
+        if not capture:
+            return
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.no_grad():                             # warm-up off the capture
+            for _ in range(max(1, warmup)):
+                self._body()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph), torch.no_grad():
+            out = self._body()
+        self._keep(out)
+
+    def _keep(self, out):
+        self.energy, self.forces = out[0], out[1]
+        self.stress = out[2] if self.cell is not None else None
+
+    def rebuild(self):
+        """Steps 1 to 5 of the chain: the list of ``self.pos`` into the capacity-sized buffers, and the graph's topology."""
+        graph.rebuild_padded(self.pos, self.batch, self._real_ptr, self.n_mol, self.cutoff, self.max_num_neighbors, self.n_pad,
+                             self._deg, self._rowptr64, self.edge_count, self.edge_index, self.edge_shift, self.edge_vec,
+                             self.edge_diff, self.state, cell=self._cell_all, inv_cell=self.inv_cell, image_range=self._ranges)
+        self.g.refresh(self.edge_index)
+
+    def model(self):
+        """The whole chain, launched eagerly: (energy, forces[, stress]) of ``self.pos``."""
+        return RebuiltStep._body(self)
+
+    def _body(self):
+        cfg, pw, g, n_all = self.cfg, self.pw, self.g, self.n_mol + 1
+        self.rebuild()
+        if self.cell is not None:
+            graph.cell_prepare(self._cell_all, self.inv_cell, self.volume)
+        g.set_geometry(self.edge_diff, self.edge_vec)     # (the fill's unshifted() / shifted(): the bits set_positions would give)
+        h, X, tape = engine.forward(cfg, pw, self.z32, g, save=True)
+        e, y, pre1 = self.head.energy_raw(h, self.z32, self.mol_ptr, n_all, mode=cfg.gemm_mode)
+        gh = self.head.grad_h_raw(pre1, cfg.F_model or cfg.F, mode=cfg.gemm_mode)
+        g_vec, g_diff = engine.backward(cfg, pw, self.z32, g, tape, gh, None)
+        f = engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
+        if self.cell is None:
+            return e[:self.n_mol], f[:self.N]
+        return e[:self.n_mol], f[:self.N], engine.virial(g, g_vec, g_diff, self.mol_ptr, n_all, self.volume)[:self.n_mol]
+
+    @torch.no_grad()
+    def __call__(self, pos: torch.Tensor, cell: Optional[torch.Tensor] = None):
+        """-> (energy [n_mol, 1], forces [N, 3]), plus stress [n_mol, 3, 3] for a periodic step."""
+        if cell is not None:
+            raise ValueError("RebuiltStep: the cell is fixed at construction (its image ranges are a host decision); a cell "
+                             "per call is refused -- use CapturedStep for a moving cell")
+        self.pos.copy_(pos)
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._keep(self._body())
+        if self.cell is None:
+            return self.energy, self.forces
+        return self.energy, self.forces, self.stress

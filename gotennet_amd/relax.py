@@ -86,13 +86,16 @@ class Relax(_ListDriver):
     ``max_num_neighbors``: as ``graph.distance_pbc``; the cell is fixed.  ``check_every``: replays between two host reads of the
     device state (the trajectory does not depend on it; replays after the last molecule has converged move nothing and are
     not counted).  ``log_len``: rows of the (energy, largest force) ring, one row per step, written BEFORE the step's move.
-    ``captured=False``: the eager reference (module docstring).
+    ``captured=False``: the eager reference (module docstring).  ``rebuild`` (a keyword of the constructor call,
+    ``Relax(..., rebuild="device")``, as for ``md.MDRun``): "host" (default) or "device": the
+    list is rebuilt inside every step on the device (``pipeline.RebuiltStep``), nothing is verified or re-recorded and
+    ``rebuilds`` stays 0 -- for relaxations whose list changes in most steps.
 
     ``run`` raises ``RuntimeError`` naming the molecule when a force is not finite; nothing of that molecule has moved.
 
     Refused with ``ValueError`` before any launch: fmax < 0; dt, dt_max or max_step not positive and finite; dt > dt_max;
     f_inc < 1; f_dec or f_alpha outside (0, 1); alpha outside (0, 1]; n_min < 0; ``fixed`` of the wrong shape or dtype; ``pos`` or
-    ``cell`` requiring grad; a cell that ``graph.resolve_images`` refuses."""
+    ``cell`` requiring grad; a cell that ``graph.resolve_images`` refuses; an unknown ``rebuild``."""
 
     def __init__(self, ef: EnergyForces, z: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, n_mol: int, fmax: float = 0.05,
                  dt: float = 0.1, dt_max: float = 1.0, max_step: float = 0.2, n_min: int = 5, f_inc: float = 1.1,

@@ -90,6 +90,33 @@ int gn_molecule_ptr(const int64_t* batch, int N, int n_mol, int* mol_ptr, void* 
  * (gotennet.py:986-989: scatter(ones, edge_index[0])).  outdeg must be zeroed by the caller. */
 int gn_out_degree(const int* src, int E, int* outdeg, void* stream);
 
+/* ---- a radius graph rebuilt inside a recorded step ------------------------------------------------------------------
+ * The searches below (gn_radius_count* / gn_radius_fill*) take rowptr and E as arguments and hold every slot to E, so a list
+ * of FIXED capacity can be refilled on the device: count over the N real atoms -> gn_degree_scan -> fill with E = capacity
+ * -> gn_padded_tail -> gn_graph_refresh.  Every entry point here is kernel launches only (no memset, no copy, no host
+ * read): a recorded chain of them holds kernel nodes only.  The sizes are graph.PaddedLayout's: capacity = e_bound + n_pad
+ * slots, n_pad dummy atoms N .. N + n_pad - 1 behind the real ones, which own the slots a step does not use. */
+
+/* Exclusive scan of the int32 degrees deg [N] into int64 rowptr64 [N + 1] (what gn_radius_fill* reads), the total also into
+ * the device word n_edges [1].  One workgroup (the scan of gn_build_csc, carry across trips of 1024 entries): what
+ * torch.cumsum and a host read of its last entry do for graph.distance. */
+int gn_degree_scan(const int* deg, int N, int64_t* rowptr64, int* n_edges, void* stream);
+
+/* The inert tail of a padded list.  E_real = rowptr64[N] is read on the device; the slots [E_real, capacity) of edge_index
+ * int64 [2, capacity], edge_shift int32 [capacity, 3] (NULL: a list without shifts), edge_vec [capacity, 3] and edge_diff
+ * [capacity] become self-loops of the dummy atoms -- src = dst = N + k, shift 0, vector 0, distance 0 -- in the balanced
+ * contiguous partition of graph.PaddedLayout.tail_degrees: of the P = capacity - E_real slots the first P % n_pad dummies
+ * get P / n_pad + 1 each, the others P / n_pad, so the list stays target-major and every dummy row holds at least one edge.
+ * One thread per slot over a grid sized by capacity - N, closed-form integer arithmetic, no atomics.  E_real outside
+ * [N, capacity - n_pad] (a count PaddedLayout's bound excludes): nothing is written and the sticky word state[0] is set. */
+int gn_padded_tail(const int64_t* rowptr64, int N, int n_pad, int64_t capacity, int64_t* edge_index, int* edge_shift,
+                   float* edge_vec, float* edge_diff, int* state, void* stream);
+
+/* gn_build_csr + gn_out_degree (outdeg NULL: not wanted) + gn_build_csc of the target-major edge_index int64 [2, E] into
+ * buffers that exist already, bit for bit what those three write; the counters are zeroed in a kernel.  work: N + E ints. */
+int gn_graph_refresh(const int64_t* edge_index, int E, int N, int* src, int* dst, int* rowptr, int* outdeg, int* colptr,
+                     int* perm, int* tgt_by_src, int* work, void* stream);
+
 /* CosineCutoff alone (layers.py:149-152): cut[e] = 0.5 (cos(pi d / cutoff) + 1) for d < cutoff, else 0.  Used when a
  * caller drives ONE GATA layer (GATA.forward, gotennet.py:366-450, takes r_ij and applies the cutoff inside message). */
 int gn_cosine_cutoff(const float* dist, int E, float cutoff, float* cut, void* stream);
