@@ -20,6 +20,7 @@ LMAX_MEAN, LMAX_MAX = 0x200, 0x400      # GN_LMAX_MEAN / GN_LMAX_MAX: the refere
 
 ACT_NONE = 11            # GN_ACT_NONE
 WGRAD_F32, WGRAD_F16X2 = 0, 2           # GN_WGRAD_*: the mode argument of gn_weight_grad_group_mode
+GEMM_FORM_BIG, GEMM_FORM_BIG8 = 1, 2    # GN_GEMM_FORM_*: the form argument of gn_gemm_group_f16x2_form
 _P, _I, _F, _L, _D = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 
 # symbol -> argtypes (mirrors include/gotennet_hip.h one for one)
@@ -79,6 +80,7 @@ SIGNATURES = {
     "gn_split_f16x2": [_P, _I, _I, _P, _P],
     "gn_split_f16x2_size": [_I, _I],
     "gn_gemm_group_f16x2": [_P, _I, _P],
+    "gn_gemm_group_f16x2_form": [_P, _I, _I, _P],
     "gn_htr_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "gn_message_backward": [_P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                             _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, C.c_long, _I, _I, _I, _I, _I, _I, _I, _P],

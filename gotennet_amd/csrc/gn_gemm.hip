@@ -11,7 +11,8 @@
 // tile; each wave a (32 TM) x (32 TN) patch of 32x32 MFMA tiles.  TM = TN = 2 for
 // the edge-sized products, TM = TN = 1 when the problem has too few 128x128 tiles to
 // fill 256 CUs (atom-sized products: a wave's chain of 64-cycle MFMAs is the latency).
-// (The plane arithmetics use 1 x 4 waves instead, SLAB_TILES and tile_plan below; small f16x2 groups leave this file for the
+// (The plane arithmetics use 1 x 4 waves instead, and f16x2 1 x 8 waves -- 512 threads, a 128 x 256 tile -- for the K-heavy edge-sized
+// products at most 256 columns wide, SLAB_TILES and tile_plan below; small f16x2 groups leave this file for the
 // K-resident panel kernel of gn_gemm_panel.hip, wide K = 256 ones for the column-loop kernel of gn_gemm_colpipe.hip.)
 // K in slabs of 32.  A and W slabs are staged through LDS as [rows][36] floats: the
 // 36-float pitch keeps ds_read_b128 conflict-free for its 16-lane service groups
@@ -82,12 +83,15 @@ __device__ __forceinline__ void store_f16x2(_Float16* d, int apl, const float4& 
 // MODE: 0 exact fp32 MFMA, 1 three bf16 planes (six MFMA terms), 2 two scaled fp16 planes (three MFMA terms, gn_gemm.h)
 template <int TM, int TN, int WM, int WN, bool PRO, int MODE, bool ASILU>
 __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
-    static_assert(WM * WN == 4, "four waves per workgroup");
+    constexpr int NW = WM * WN, NT = 64 * NW;       // waves and threads of the workgroup
+    static_assert(NW == 4 || (NW == 8 && MODE == 2 && WM == 1), "four waves per workgroup, or 1 x 8 in the f16x2 arithmetic");
     constexpr bool SPLIT = MODE != 0;
     constexpr bool F16 = MODE == 2;
     constexpr int NP = F16 ? 2 : 3;                 // operand planes
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr int RA = BM / 32, RB = BN / 32;       // staged float4 rows per thread
+    constexpr int SRS = 8 * NW;                     // rows one staging pass of the workgroup covers (8 float4 columns per row)
+    constexpr int RA = BM / SRS, RB = BN / SRS;     // staged float4 rows per thread
+    constexpr int EG = NW / 4;                      // F16: dwords of block exponents per slab buffer
     constexpr int STAGE = (BM + BN) * PITCH;        // floats per K-slab buffer (A rows then W rows)
     constexpr int CP = BN + 4;                      // epilogue tile pitch
     constexpr int APL = BM * SPLIT_PB;              // SPLIT: bf16 elements per A plane of a slab
@@ -97,10 +101,18 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
     // F16: + the block exponents of the two slab buffers, [2][4] signed bytes: wave q stages rows 8q..8q+7 of every
     // 32-row M-tile, and those rows -- accumulator registers 4q..4q+3 of every MFMA tile -- share ONE exponent per slab.
     // One dword per slab buffer, so "did anything change" is a single scalar compare per slab.
-    __shared__ __attribute__((aligned(16))) float smem[LDS_FLOATS + (F16 ? 2 : 0)];
+    // Eight waves (1 x 8, BM = 128): a staging pass covers 64 rows, so wave w stages rows 8 (w & 3) .. + 7 of the M-tiles
+    // (w >> 2) and (w >> 2) + 2 -- 16 rows, and a 32-row block of the four-wave form is split between waves q and q + 4.  Giving both
+    // halves ONE exponent would take a second workgroup barrier per slab (each wave's maximum is known only when its rows have
+    // landed, right before the split), so the row grouping CHANGES here: every wave keeps its own exponent, [2][8] bytes, and
+    // byte q of dword (i & 1) belongs to the accumulator registers 4q..4q+3 of M-tile i.  Blocks of 16 rows instead of 32: never a
+    // larger exponent than the four-wave form's, the same per-row bound, but not the same bits.
+    __shared__ __attribute__((aligned(16))) float smem[LDS_FLOATS + (F16 ? 2 * EG : 0)];
     signed char* const exps = reinterpret_cast<signed char*>(smem + LDS_FLOATS);
     int e_run = -120;                               // F16, staging side: running exponent of this wave's rows
-    unsigned e_acc = 0x88888888u;                   // F16, MFMA side: the four block exponents (bytes) the accumulators are held in
+    unsigned e_acc[EG];                             // F16, MFMA side: the block exponents (bytes) the accumulators are held in; M-tile i: e_acc[i % EG]
+#pragma unroll
+    for (int g = 0; g < EG; ++g) e_acc[g] = 0x88888888u;
     int ewt = 0;                                    // F16: the weight tensor's exponent (header of the packed planes)
 
     // ---- the tile walk: the XCD ranges, select, set_tile.  One launch walks the tiles of up to GN_MAX_GROUP independent
@@ -160,7 +172,7 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    const int c4 = tid & 7;                         // staging map: thread -> (row sr + 32 i, float4 column c4)
+    const int c4 = tid & 7;                         // staging map: thread -> (row sr + SRS i, float4 column c4)
     const int sr = tid >> 3;
     const int stride = gridDim.x >> 3;
 
@@ -176,14 +188,14 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
         a_full = m0f + BM <= p.M && (p.K % BK) == 0;
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
-            const int gm = m0f + sr + 32 * i;
+            const int gm = m0f + sr + SRS * i;
             aok[i] = gm < p.M;
             prow[i] = phys_row(p, aok[i] ? gm : 0);
         }
         if constexpr (!SPLIT) {
 #pragma unroll
             for (int i = 0; i < RB; ++i) {
-                const int gn = n0f + sr + 32 * i;
+                const int gn = n0f + sr + SRS * i;
                 bok[i] = gn < p.N;
                 brow[i] = p.W + (size_t)(bok[i] ? gn : 0) * p.K + 4 * c4;
             }
@@ -230,8 +242,8 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
         e_run = need > e_run ? need : e_run;
         const float scale = exp_scale(e_run);
 #pragma unroll
-        for (int i = 0; i < RA; ++i) store_f16x2(d0 + 32 * i * SPLIT_PB, APL, v[i], scale);
-        if (lane == 0) exps[sb * 4 + wave] = (signed char)e_run;
+        for (int i = 0; i < RA; ++i) store_f16x2(d0 + SRS * i * SPLIT_PB, APL, v[i], scale);
+        if (lane == 0) exps[sb * NW + wave] = (signed char)e_run;
     };
     // ... and the three bf16 planes of the staged rows
     auto stash_bf16 = [&](int sb, const float4 (&v)[RA]) {
@@ -240,7 +252,7 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
         for (int i = 0; i < RA; ++i) {
             bf16x4 h, m, l;
             split4_trunc(v[i], h, m, l);
-            __bf16* d = d0 + 32 * i * SPLIT_PB;
+            __bf16* d = d0 + SRS * i * SPLIT_PB;
             *reinterpret_cast<bf16x4*>(d) = h;
             *reinterpret_cast<bf16x4*>(d + APL) = m;
             *reinterpret_cast<bf16x4*>(d + 2 * APL) = l;
@@ -302,9 +314,9 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
         } else {
             float* buf = smem + sb * STAGE;
 #pragma unroll
-            for (int i = 0; i < RA; ++i) st4(&buf[(sr + 32 * i) * PITCH + 4 * c4], qa[i]);
+            for (int i = 0; i < RA; ++i) st4(&buf[(sr + SRS * i) * PITCH + 4 * c4], qa[i]);
 #pragma unroll
-            for (int i = 0; i < RB; ++i) st4(&buf[(BM + sr + 32 * i) * PITCH + 4 * c4], qb[i]);
+            for (int i = 0; i < RB; ++i) st4(&buf[(BM + sr + SRS * i) * PITCH + 4 * c4], qb[i]);
         }
     };
     // ---- planes: the weights.  B operands of k-step g (16 deep) for this wave's TN column blocks, NP planes each, L2 -> registers
@@ -333,10 +345,27 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
     // F16: bring the accumulator rows of every 8-row block to the exponent slab buffer `sb` was staged with.  The
     // exponents only grow and settle after the first slabs: the common case is TM scalar compares that all fall through.
     auto rescale = [&](int sb) {
-        const unsigned en = (unsigned)__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(exps + sb * 4));
-        if (__builtin_expect(en != e_acc, 0)) {
-            rescale_rows(&acc[0][0], TM * TN, e_acc, en);
-            e_acc = en;
+        if constexpr (EG == 1) {
+            const unsigned en = (unsigned)__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(exps + sb * 4));
+            if (__builtin_expect(en != e_acc[0], 0)) {
+                rescale_rows(&acc[0][0], TM * TN, e_acc[0], en);
+                e_acc[0] = en;
+            }
+        } else {
+            // eight waves: M-tile i was staged by the waves q + 4 (i & 1), dword i & 1 of the slab's exponents
+            unsigned en[EG];
+            bool same = true;
+#pragma unroll
+            for (int g = 0; g < EG; ++g) {
+                en[g] = (unsigned)__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(exps + sb * NW + 4 * g));
+                same = same && en[g] == e_acc[g];
+            }
+            if (__builtin_expect(!same, 0)) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i) rescale_rows(&acc[i][0], TN, e_acc[i % EG], en[i % EG]);
+#pragma unroll
+                for (int g = 0; g < EG; ++g) e_acc[g] = en[g];
+            }
         }
     };
 
@@ -390,14 +419,27 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
     // weights of k-step 2kt+2: nothing that is needed soon ever queues behind an A load younger than one slab time.
     // sched_barrier(0) keeps the phases apart (without them the scheduler hoists across the whole region until the
     // 256-register budget spills: measured 15-30 % slower).
-    auto loop_planes_ahead = [&](int nk, uint4 (&bq)[2][TN][NP]) {
+    // EARLY (eight waves, GN_F16_BIG8_PHASED): the two waves of a SIMD (w and w + 4) run the phases of a slab in OPPOSITE order.
+    // All eight waves meet at one barrier per slab, so left alone they multiply at the same time and split at the same time:
+    // the matrix pipe idles while both waves of a SIMD are in their split.  An early wave writes slab kt + 1 to LDS FIRST (the
+    // other buffer: last read before the barrier that ended slab kt - 1) and multiplies slab kt after it, while its partner
+    // multiplies first and splits last.  Its A slabs stay two slab times in flight as well: it requests slab kt + 3 right after the
+    // split, into the registers the split freed (past K the loads are clamped to valid memory and never used).
+    auto loop_planes_ahead = [&](int nk, uint4 (&bq)[2][TN][NP], auto EARLY) {
+        constexpr bool early = decltype(EARLY)::value;
         const __bf16* const Abase = reinterpret_cast<const __bf16*>(smem) + (wm * 32 * TM + (lane & 31)) * SPLIT_PB + (lane >> 5) * 8;
         auto slab = [&](int kt, auto SET, auto LAST) {
             constexpr int set = decltype(SET)::value;            // register set of slab kt (= kt & 1)
             constexpr bool last = decltype(LAST)::value;
             const __bf16* Ap = Abase + set * STAGE_S;
             load_b(2 * kt + 1, bq[1]);
-            if constexpr (!last) fetchA((kt + 2) * BK, qa2[set], kok2[set]);   // slab kt + 2 -> the set slab kt came from
+            if constexpr (!early) {
+                if constexpr (!last) fetchA((kt + 2) * BK, qa2[set], kok2[set]);   // slab kt + 2 -> the set slab kt came from
+            } else if constexpr (!last) {
+                stashA(set ^ 1, qa2[set ^ 1], kok2[set ^ 1]);                      // slab kt + 1 -> the other LDS buffer
+                __builtin_amdgcn_sched_barrier(0);
+                fetchA((kt + 3) * BK, qa2[set ^ 1], kok2[set ^ 1]);                // slab kt + 3 -> the set that was just split
+            }
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (F16) rescale(set);
             kstep(Ap, 0, bq[0]);
@@ -405,12 +447,13 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
             if constexpr (!last) load_b(2 * kt + 2, bq[0]);
             kstep(Ap, 1, bq[1]);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!last) stashA(set ^ 1, qa2[set ^ 1], kok2[set ^ 1]);  // slab kt + 1 -> the other LDS buffer
+            if constexpr (!last && !early) stashA(set ^ 1, qa2[set ^ 1], kok2[set ^ 1]);  // slab kt + 1 -> the other LDS buffer
             __syncthreads();
         };
         using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>;
         using No = std::false_type; using Yes = std::true_type;
         fetchA(BK, qa2[1], kok2[1]);             // slab 1 (zero-filled past K); slab 0 is already staged
+        if constexpr (early) fetchA(2 * BK, qa2[0], kok2[0]);
         int kt = 0;
         for (; kt + 2 < nk; kt += 2) {
             slab(kt, T0{}, No{});
@@ -442,7 +485,8 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
         if constexpr (F16) {
             e_run = -120;
-            e_acc = 0x88888888u;                         // -120 in every byte (the accumulators are zero)
+#pragma unroll
+            for (int g = 0; g < EG; ++g) e_acc[g] = 0x88888888u;   // -120 in every byte (the accumulators are zero)
         }
         stash(0, pa, pb);
         uint4 bq[2][TN][NP];
@@ -451,7 +495,10 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
             load_b(0, bq[0]);
         }
         __syncthreads();
-        if constexpr (AHEAD) loop_planes_ahead(nk, bq);
+        if constexpr (AHEAD && NW == 8 && GN_F16_BIG8_PHASED) {
+            if (GN_F16_BIG8_PHASED == 2 ? (__builtin_amdgcn_readfirstlane(wave) & 1) : (__builtin_amdgcn_readfirstlane(wave) >= 4)) loop_planes_ahead(nk, bq, std::true_type{});
+            else loop_planes_ahead(nk, bq, std::false_type{});
+        } else if constexpr (AHEAD) loop_planes_ahead(nk, bq, std::false_type{});
         else if constexpr (SPLIT) {
             // Planes with a prologue, the conditional form, in place (as a lambda the [54368 x 256 x 1536] prologue launch
             // measured 2.5 % slower): weights, MFMAs and the split each in their own basic block.  (A branch-free single
@@ -537,12 +584,12 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
                 for (int r = 0; r < 16; ++r) {
                     const int row = wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                     float v = acc[i][j][r];
-                    if constexpr (F16) v = ldexpf(v, (int)(signed char)(e_acc >> (8 * (r >> 2))) + ewt);   // back from the block / weight exponents (only the RESULT may under- / overflow)
+                    if constexpr (F16) v = ldexpf(v, (int)(signed char)(e_acc[i % EG] >> (8 * (r >> 2))) + ewt);   // back from the block / weight exponents (only the RESULT may under- / overflow)
                     smem[row * CP + wn * 32 * TN + j * 32 + (lane & 31)] = v;
                 }
         __syncthreads();
         {
-            constexpr int C4 = BN / 4;                  // 256 % C4 == 0: a thread keeps ONE column group
+            constexpr int C4 = BN / 4;                  // NT % C4 == 0: a thread keeps ONE column group
             const int cc = (tid % C4) * 4, gn = n0 + cc;
             if (gn < p.N) {
                 const float4 bias4 = p.bias ? ld4(p.bias + gn) : zero4();
@@ -552,14 +599,14 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
                     // four rows per pass, all residual / gate loads of the pass issued BEFORE its first store: the
                     // stores may alias them as far as the compiler knows (res == C is allowed), and a load behind
                     // a store was one exposed round trip per row
-                    constexpr int ITS = (BM * C4) / 256, UN = ITS < 4 ? ITS : 4;
+                    constexpr int ITS = (BM * C4) / NT, UN = ITS < 4 ? ITS : 4;
                     for (int it0 = 0; it0 < ITS; it0 += UN) {
                         size_t off[UN];
                         bool ok[UN];
                         float4 rv[UN], gv[UN];
 #pragma unroll
                         for (int u = 0; u < UN; ++u) {
-                            const int gm = m0 + (it0 + u) * (256 / C4) + tid / C4;
+                            const int gm = m0 + (it0 + u) * (NT / C4) + tid / C4;
                             ok[u] = gm < p.M;
                             off[u] = (size_t)phys_row(p, ok[u] ? gm : 0) * p.ldc + gn;
                             rv[u] = (ok[u] && p.res) ? ld4(p.res + off[u]) : zero4();
@@ -568,7 +615,7 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
 #pragma unroll
                         for (int u = 0; u < UN; ++u) {
                             if (!ok[u]) continue;
-                            const int row = (it0 + u) * (256 / C4) + tid / C4;
+                            const int row = (it0 + u) * (NT / C4) + tid / C4;
                             // the chain of epi_store (gn_gemm.h) stated in place: through the function the exact-fp32
                             // prologue kernel without a compile-time activation took 100 VGPRs instead of 94
                             float4 v = ld4(&smem[row * CP + cc]) + bias4;
@@ -581,8 +628,8 @@ __device__ __forceinline__ void gemm_body(const GroupArgs ga) {
                     }
                 } else {
 #pragma unroll 4
-                    for (int it = 0; it < (BM * C4) / 256; ++it) {
-                        const int row = it * (256 / C4) + tid / C4;
+                    for (int it = 0; it < (BM * C4) / NT; ++it) {
+                        const int row = it * (NT / C4) + tid / C4;
                         const int gm = m0 + row;
                         if (gm >= p.M) continue;
                         const float4 x = ld4(&smem[row * CP + cc]);
@@ -619,9 +666,10 @@ __global__ __launch_bounds__(256, GN_SPLIT_MINW) void gemm_bf16x3_mfma(const Gro
     gemm_body<TM, TN, WM, WN, PRO, 1, ASILU>(ga);
 }
 
-// 2 x fp16-split instantiation (three MFMA terms per product, block exponents): same grid and tile shapes
+// 2 x fp16-split instantiation (three MFMA terms per product, block exponents): same grid and tile shapes, and the 1 x 8-wave
+// form (512 threads: ONE workgroup per CU holds the two waves per SIMD that two four-wave workgroups hold)
 template <int TM, int TN, int WM, int WN, bool PRO, bool ASILU>
-__global__ __launch_bounds__(256, GN_SPLIT_MINW) void gemm_f16x2_mfma(const GroupArgs ga) {
+__global__ __launch_bounds__(64 * WM * WN, GN_SPLIT_MINW) void gemm_f16x2_mfma(const GroupArgs ga) {
     gemm_body<TM, TN, WM, WN, PRO, 2, ASILU>(ga);
 }
 
@@ -633,23 +681,23 @@ using gn::GemmArgs;
 using SlabKernel = void (*)(const gn::GroupArgs);
 
 // ---- the slab tiles: the wave layout of every (arithmetic, tile) that is built; TM = 0: not built ----------------------
-enum Tile { TILE_BIG, TILE_MID, TILE_WIDE, TILE_SMALL, TILE_COUNT };
+enum Tile { TILE_BIG, TILE_MID, TILE_WIDE, TILE_SMALL, TILE_BIG8, TILE_COUNT };
 struct TileShape {
     int TM, TN, WM, WN;
     constexpr int BM() const { return 32 * TM * WM; }
     constexpr int BN() const { return 32 * TN * WN; }
 };
 constexpr TileShape SLAB_TILES[3][TILE_COUNT] = {
-    //  big 128 x 128   mid 64 x 128    wide 32 x 128   small 64 x 64
-    {{2, 2, 2, 2}, {0, 0, 0, 0}, {0, 0, 0, 0}, {1, 1, 2, 2}},       // exact fp32
-    {{4, 1, 1, 4}, {0, 0, 0, 0}, {0, 0, 0, 0}, {1, 1, 2, 2}},       // bf16x3
-    {{4, 1, 1, 4}, {2, 1, 1, 4}, {1, 1, 1, 4}, {1, 1, 2, 2}},       // f16x2
+    //  big 128 x 128   mid 64 x 128    wide 32 x 128   small 64 x 64   big8 128 x 256 (eight waves, no prologue)
+    {{2, 2, 2, 2}, {0, 0, 0, 0}, {0, 0, 0, 0}, {1, 1, 2, 2}, {0, 0, 0, 0}},       // exact fp32
+    {{4, 1, 1, 4}, {0, 0, 0, 0}, {0, 0, 0, 0}, {1, 1, 2, 2}, {0, 0, 0, 0}},       // bf16x3
+    {{4, 1, 1, 4}, {2, 1, 1, 4}, {1, 1, 1, 4}, {1, 1, 2, 2}, {4, 1, 1, 8}},       // f16x2
 };
 
 template <int MODE, int T, bool PRO, bool ASILU>
 SlabKernel slab_kernel() {
     constexpr TileShape s = SLAB_TILES[MODE][T];
-    if constexpr (s.TM == 0) return nullptr;
+    if constexpr (s.TM == 0 || (T == TILE_BIG8 && PRO)) return nullptr;
     else if constexpr (MODE == 0) return gn::gemm_f32_mfma<s.TM, s.TN, s.WM, s.WN, PRO, ASILU>;
     else if constexpr (MODE == 1) return gn::gemm_bf16x3_mfma<s.TM, s.TN, s.WM, s.WN, PRO, ASILU>;
     else return gn::gemm_f16x2_mfma<s.TM, s.TN, s.WM, s.WN, PRO, ASILU>;
@@ -665,21 +713,31 @@ SlabKernel slab_kernel(Tile t, bool pro, bool silu) {
     case TILE_BIG: return slab_kernel<MODE, TILE_BIG>(pro, silu);
     case TILE_MID: return slab_kernel<MODE, TILE_MID>(pro, silu);
     case TILE_WIDE: return slab_kernel<MODE, TILE_WIDE>(pro, silu);
+    case TILE_BIG8: return slab_kernel<MODE, TILE_BIG8>(pro, silu);
     default: return slab_kernel<MODE, TILE_SMALL>(pro, silu);
     }
 }
 
 // The slab tile of a group and the cap of its persistent grid (2 / 3 / 4 workgroups per CU walk the tile list: +2 %)
 struct TilePlan { Tile tile; long cap; };
-TilePlan tile_plan(const GemmArgs* g, int n, int split) {
+// form: GN_GEMM_FORM_* of gn_gemm_group_f16x2_form -- 0: the routing below; otherwise the caller names the 128-row tile
+TilePlan tile_plan(const GemmArgs* g, int n, int split, bool pro, int form) {
+    if (form == GN_GEMM_FORM_BIG) return {TILE_BIG, GN_GEMM_BIG_CAP};
+    if (form == GN_GEMM_FORM_BIG8) return {TILE_BIG8, GN_F16_BIG8_CAP};
     long big = 0, rows_all = 0;
     bool wide = GN_F16_SMALL_WIDE && split == 2, gated = false;
+    bool big8 = GN_F16_BIG8_MIN_K > 0 && split == 2 && !pro && g[0].K >= GN_F16_BIG8_MIN_K && g[0].N > 128;
     for (int i = 0; i < n; ++i) {
         big += (long)((g[i].M + 127) / 128) * ((g[i].N + 127) / 128);
         wide = wide && g[i].N >= 128;
+        big8 = big8 && g[i].N <= 256;
         rows_all += g[i].M;
         gated = gated || (g[i].gate != nullptr && g[i].res != nullptr);
     }
+    // f16x2, edge-sized K-heavy groups at most 256 columns wide (the input-gradient products dL/dt = [g_eproj | g_pre_t] W + gt
+    // and their riders): 128 x 256 tiles of 1 x 8 waves -- an A slab is fetched, scaled and split ONCE per row panel
+    // instead of once per 128 columns (GN_F16_BIG8_MIN_K, gn_tune.h; profiles/dt_wide_ab.txt)
+    if (big8 && big >= (long)GN_GEMM_BIG_MIN) return {TILE_BIG8, GN_F16_BIG8_CAP};
     // 128x128 tiles from GN_GEMM_BIG_MIN = 900 tiles up (measured switch-over; a build-time constant of gn_tune.h, swept
     // with tools/variants.py): the [E x 256 x K] products (850 tiles = 1.66 rounds on 512 resident workgroups) run
     // 4-20 % faster as 3400 64x64 tiles, the [E x 1536 x 256] product (5100 tiles) and the four-problem X group (1008)
@@ -697,8 +755,14 @@ TilePlan tile_plan(const GemmArgs* g, int n, int split) {
 }
 
 // the slab kernel: every group
-int slab_launch(const GemmArgs* g, int n, hipStream_t st, int split) {
-    const TilePlan plan = tile_plan(g, n, split);
+int slab_launch(const GemmArgs* g, int n, hipStream_t st, int split, int form = 0) {
+    bool pro = false, silu = true;
+    for (int i = 0; i < n; ++i) {
+        pro = pro || g[i].pro_mode != 0 || g[i].a_gate != nullptr;
+        silu = silu && g[i].act_kind == GN_ACT_SILU;
+    }
+    if (form != 0 && (split != 2 || (form == GN_GEMM_FORM_BIG8 && pro))) return GN_ERR_BAD_ARG;
+    const TilePlan plan = tile_plan(g, n, split, pro, form);
     const TileShape shape = SLAB_TILES[split][plan.tile];
     gn::GroupArgs ga;
     const long tiles = gn::fill_group(ga, ga.tile_end, g, n, shape.BM(), shape.BN());
@@ -706,18 +770,15 @@ int slab_launch(const GemmArgs* g, int n, hipStream_t st, int split) {
     // per-problem XCD ranges when the problems are unlike (different tile lengths K, or a small problem riding with
     // a large one: its tiles would otherwise all sit at the end of the last XCD's range)
     ga.spread = 0;
-    bool pro = false, silu = true;
     for (int i = 0; i < n; ++i) {
         const long t0 = ga.tile_end[0], ti = ga.tile_end[i] - (i ? ga.tile_end[i - 1] : 0);
         ga.spread |= (g[i].K != g[0].K) || ti * 4 < t0 || t0 * 4 < ti;
-        pro = pro || g[i].pro_mode != 0 || g[i].a_gate != nullptr;
-        silu = silu && g[i].act_kind == GN_ACT_SILU;
     }
     long grid = 8L * ((tiles + 7) / 8);
     if (grid > plan.cap) grid = plan.cap;
     const SlabKernel k = split == 2 ? slab_kernel<2>(plan.tile, pro, silu)
                        : split == 1 ? slab_kernel<1>(plan.tile, pro, silu) : slab_kernel<0>(plan.tile, pro, silu);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), 0, st, ga);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * shape.WM * shape.WN), 0, st, ga);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }
@@ -770,7 +831,8 @@ GemmArgs make_args(const gn_gemm_desc& q) {
 //      {128, 256, 512} or depths that are all multiples of 256;
 //   2. f16x2: the column-loop kernel -- SiLU, no prologue, no K segments, K = 256, a product >= GN_CP_MIN_N columns wide
 //      and >= GN_CP_MIN_TILES tiles of 64 x 128;   3. the slab kernel of this file: everything else, every arithmetic.
-int gemm_launch(const GemmArgs* g, int n, hipStream_t st, int split) {
+int gemm_launch(const GemmArgs* g, int n, hipStream_t st, int split, int form) {
+    if (form != 0) return slab_launch(g, n, st, split, form);
     if (split == 2) {
         int r = gn_gemm_panel_launch(g, n, st);
         if (r == 0) r = gn_gemm_colpipe_launch(g, n, st);
@@ -779,7 +841,7 @@ int gemm_launch(const GemmArgs* g, int n, hipStream_t st, int split) {
     return slab_launch(g, n, st, split);
 }
 
-int gemm_group_impl(const gn_gemm_desc* d, int n, void* stream, int split) {
+int gemm_group_impl(const gn_gemm_desc* d, int n, void* stream, int split, int form = 0) {
     if (n < 0 || n > gn::GN_MAX_GROUP || (n > 0 && !d)) return GN_ERR_BAD_ARG;
     GemmArgs g[gn::GN_MAX_GROUP];
     int m = 0;
@@ -788,7 +850,7 @@ int gemm_group_impl(const gn_gemm_desc* d, int n, void* stream, int split) {
         if (d[i].M != 0) g[m++] = make_args(d[i]);
     }
     if (m == 0) return GN_OK;
-    return gemm_launch(g, m, (hipStream_t)stream, split);
+    return gemm_launch(g, m, (hipStream_t)stream, split, form);
 }
 
 // the single-problem entries: a group of one (no K segments).  They refuse a bad act_kind even at M == 0, the group entries
@@ -814,6 +876,11 @@ extern "C" int gn_gemm_group(const gn_gemm_desc* d, int n, void* stream) { retur
 extern "C" int gn_gemm_group_split(const gn_gemm_desc* d, int n, void* stream) { return gemm_group_impl(d, n, stream, 1); }
 // ... and on the 2 x fp16-split path: every desc.W points to the buffer written by gn_split_f16x2
 extern "C" int gn_gemm_group_f16x2(const gn_gemm_desc* d, int n, void* stream) { return gemm_group_impl(d, n, stream, 2); }
+// ... on the slab kernel's 128-row tile the caller names, whatever the routing would choose (A/B probes and tests)
+extern "C" int gn_gemm_group_f16x2_form(const gn_gemm_desc* d, int n, int form, void* stream) {
+    if (form != GN_GEMM_FORM_BIG && form != GN_GEMM_FORM_BIG8) return GN_ERR_BAD_ARG;
+    return gemm_group_impl(d, n, stream, 2, form);
+}
 
 extern "C" int gn_gemm_ex(const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int Mrows, int Nout,
         int K, int act_lo, int act_hi, int row_cnt, int row_gstride, int row_goff, const float* res, const float* gate,

@@ -110,6 +110,21 @@
 #ifndef GN_F16_SMALL_CAP
 #define GN_F16_SMALL_CAP 1024     // persistent workgroups of that kernel
 #endif
+#ifndef GN_F16_BIG8_MIN_K
+#define GN_F16_BIG8_MIN_K 1024   // f16x2 big-tile groups without prologue, every N <= 256, leading problem wider than 128 columns and at least
+                                 // this deep: 128 x 256 tiles of 1 x 8 waves (512 threads) instead of 128 x 128 (0: never).  In the C2 step
+                                 // [54368 x 256 x 1792 + riders] 219.1 -> 197.8 us, K = 1536 180.0 -> 161.9, K = 1280 165.7 -> 151.4; the gated
+                                 // K = 256 launch loses stand-alone (79.5 -> 80.9 us against the 128 x 128 tile, 76.6 on its own 64 x 128 tile).
+                                 // Between them only a plain K = 768 group was probed (stand-alone 50.6 -> 47.0 us) and none in the step: the
+                                 // crossover lies in 256 < K <= 768 and 1024 is the smallest depth measured in the step (profiles/dt_wide_ab.txt)
+#endif
+#ifndef GN_F16_BIG8_CAP
+#define GN_F16_BIG8_CAP 256      // persistent workgroups of that kernel (one per CU: eight waves, two per SIMD)
+#endif
+#ifndef GN_F16_BIG8_PHASED
+#define GN_F16_BIG8_PHASED 1     // that kernel: waves 4..7 split the next slab BEFORE they multiply the current one, waves 0..3 after (0: all after; 2: the odd waves
+                                 // before).  Stand-alone [54368 x 256 x 1792], cold: 207.3 (0) / 200.2 (1) / 203.1 us (2), four-wave tile 216.9
+#endif
 #ifndef GN_HTR_CLOSED
 #define GN_HTR_CLOSED 1        // htr_edge_kernel at lmax = 3: closed form EQ.EK - (2 - r.r)(EQ.r)(EK.r) instead of two rejections
 #endif

@@ -276,10 +276,13 @@ def gemm(A, lda, W, bias, C, ldc, rows, nout, K, act=(0, 0), rowmap=(1, 1, 0), r
          ptr(a_gate), ldg, 0 if kind is None else kind, _stream())
 
 
-def gemm_group(problems, mode=None, kind=None):
+def gemm_group(problems, mode=None, kind=None, form=0):
     """Several INDEPENDENT ``gemm(...)`` calls (a list of argument dicts) as ONE launch (gn_gemm_group, or
-    gn_gemm_group_split / _f16x2 with the weights replaced by their cached planes)."""
+    gn_gemm_group_split / _f16x2 with the weights replaced by their cached planes).  ``form``: a GN_GEMM_FORM_* tile of the
+    f16x2 slab kernel in place of the routed kernel (gn_gemm_group_f16x2_form: probes and tests)."""
     mode = resolve_mode(mode)
+    if form and mode != "f16x2":
+        raise ValueError("a named slab-kernel form is an f16x2 launch")
     kind = 0 if kind is None else kind
     problems = [q for q in problems if q is not None]
     split = mode in _PLANE_MODES
@@ -308,6 +311,9 @@ def gemm_group(problems, mode=None, kind=None):
             d.A2, d.A3, d.a_seg = ptr(g("A2")), ptr(g("A3")), g("a_seg", 0)
             d.act_kind = g("kind", kind)
             d.lda2 = g("lda2", 0)
+        if form:
+            call("gn_gemm_group_f16x2_form", arr, len(chunk), form, _stream())
+            continue
         call(_PLANE_MODES[mode][1] if split else "gn_gemm_group", arr, len(chunk), _stream())
 
 

@@ -237,7 +237,7 @@ int gn_gemm_group_split(const gn_gemm_desc* problems, int n, void* stream);
  * found on the device, no host read-back).  A is scaled per (staging wave, K-slab of 32 columns) by the running maximum
  * of that block's binary exponent (exact powers of two, accumulators rescaled when it grows): wave q of four stages rows
  * 8q..8q+7 of every 32-row MFMA tile of the workgroup tile, so 16 rows (64-row tiles) or 32 rows (128-row tiles) share
- * an exponent -- results are bit-reproducible but depend at the 1e-7 level on which rows are neighbours (INTEGRATION.md:
+ * an exponent (the eight-wave 128 x 256 tile, GN_GEMM_FORM_BIG8 below: 16 rows) -- results are bit-reproducible but depend at the 1e-7 level on which rows are neighbours (INTEGRATION.md:
  * batch-position contract; per-row bound: tests/test_hip_parity.py::test_fp16_block_exponent_per_row_bound).  Each scaled
  * operand is split into two fp16 planes, and
  * the product accumulated in fp32 from THREE plane pairs on v_mfma_f32_32x32x16_f16 -- half the matrix work of the
@@ -251,6 +251,15 @@ int gn_gemm_f16x2(const float* A, int lda, const unsigned short* W2, const float
                   int pro_mode, int pro_lo, int pro_hi, const float* a_pre, int ldp,
                   const float* a_gate, int ldg, int act_kind, void* stream);
 int gn_gemm_group_f16x2(const gn_gemm_desc* problems, int n, void* stream);
+/* The same group on a NAMED 128-row tile of the slab kernel instead of the routed kernel (no prologue for BIG8; otherwise
+ * GN_ERR_BAD_ARG): GN_GEMM_FORM_BIG = 128 x 128, four waves, 32 rows per block exponent; GN_GEMM_FORM_BIG8 = 128 x 256, eight
+ * waves -- an A slab is scaled and split once per row panel; the eight staging waves each keep their own exponent, so 16 rows
+ * (rows 8q..8q+7 of the M-tiles i and i + 2 of the panel) share one: same per-row bound, not the same bits as BIG.
+ * gn_gemm_group_f16x2 routes edge-sized groups with N <= 256 and a K-heavy leading problem to BIG8 (csrc/gn_tune.h).  For A/B
+ * probes and for tests that hold one form against the other at small shapes. */
+#define GN_GEMM_FORM_BIG 1
+#define GN_GEMM_FORM_BIG8 2
+int gn_gemm_group_f16x2_form(const gn_gemm_desc* problems, int n, int form, void* stream);
 
 /* ---- K6 GATA message / softmax / aggregate -------------------------------------------- */
 /* Attention weights (gotennet.py:497-511): s[e,h] = sum_{c in head h} q[i,c] k[j,c] t_attn[e,c];
