@@ -150,7 +150,9 @@ def _ordered_worker(rank, world, port, B, steps, lanes, q):
         assert out is red.bufs[s % lanes]
         seen.append(out.clone())
     red.wait()
-    q.put((rank, [tuple(o) for o in red.order], torch.stack(seen)))
+    # (as a numpy array: pickled by value.  A tensor travels as a shared-memory handle the parent must fetch from THIS
+    #  process, which may have exited by then: FileNotFoundError in the parent's q.get)
+    q.put((rank, [tuple(o) for o in red.order], torch.stack(seen).numpy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -173,4 +175,4 @@ def test_ordered_reducer_two_ranks_three_lanes():
                         for s in range(steps)])
     for rank, order, seen in res:
         assert order == [(s, s % lanes) for s in range(steps)]
-        assert torch.equal(seen, want)                # step s of rank 0 met step s of rank 1, every shard exactly once
+        assert torch.equal(torch.from_numpy(seen), want)                # step s of rank 0 met step s of rank 1, every shard exactly once
