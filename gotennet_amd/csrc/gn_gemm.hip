@@ -826,7 +826,24 @@ GemmArgs make_args(const gn_gemm_desc& q) {
     return p;
 }
 
+// The K-concatenated input-gradient of the X products, gX1 = gX + [gXp | gEQ | gEK_l] [W_vu^T | W_vq^T | W_vk_l^T]^T per degree
+// block, and groups like it -- f16x2, no prologue, EVERY problem K-segmented, at least 768 deep and 129 .. 256 columns wide,
+// GN_F16_XCAT_MIN_ROWS rows or more in the group: the eight-wave 128 x 256 tile, ahead of the panel kernel (32 x 128 tiles:
+// the weight fragments of a 768-deep product are re-read from L2 for every 32 rows, an A row is converted for each of the
+// two column tiles).  Below the row threshold the panel kernel keeps them (gn_tune.h; profiles/xside_ab.txt).
+bool xcat_big8(const GemmArgs* g, int n) {
+    if (GN_F16_XCAT_MIN_ROWS <= 0) return false;
+    long rows = 0;
+    for (int i = 0; i < n; ++i) {
+        if (g[i].pro_mode != 0 || g[i].a_gate != nullptr || g[i].a_seg == 0 || g[i].K < 768 || g[i].N > 256 || g[i].N <= 128)
+            return false;
+        rows += g[i].M;
+    }
+    return rows >= (long)GN_F16_XCAT_MIN_ROWS;
+}
+
 // One launch for a validated group (GemmArgs from make_args: nt_store included); split: 0 exact fp32, 1 bf16x3, 2 f16x2).  The routing, in this order (each launcher states its conditions in full):
+//   0. f16x2: the eight-wave slab tile for K-segmented groups with many rows (xcat_big8 above);
 //   1. f16x2: the K-resident panel kernel -- no prologue, at most GN_GEMM_PANEL_MAX tiles of 32 x 128, one depth K in
 //      {128, 256, 512} or depths that are all multiples of 256;
 //   2. f16x2: the column-loop kernel -- SiLU, no prologue, no K segments, K = 256, a product >= GN_CP_MIN_N columns wide
@@ -834,6 +851,7 @@ GemmArgs make_args(const gn_gemm_desc& q) {
 int gemm_launch(const GemmArgs* g, int n, hipStream_t st, int split, int form) {
     if (form != 0) return slab_launch(g, n, st, split, form);
     if (split == 2) {
+        if (xcat_big8(g, n)) return slab_launch(g, n, st, split, GN_GEMM_FORM_BIG8);
         int r = gn_gemm_panel_launch(g, n, st);
         if (r == 0) r = gn_gemm_colpipe_launch(g, n, st);
         if (r != 0) return r > 0 ? GN_OK : -r;

@@ -118,6 +118,13 @@
                                  // Between them only a plain K = 768 group was probed (stand-alone 50.6 -> 47.0 us) and none in the step: the
                                  // crossover lies in 256 < K <= 768 and 1024 is the smallest depth measured in the step (profiles/dt_wide_ab.txt)
 #endif
+#ifndef GN_F16_XCAT_MIN_ROWS
+#define GN_F16_XCAT_MIN_ROWS 16384 // f16x2 groups without prologue whose problems are ALL K-segmented, at least 768 deep and 129 .. 256 columns wide
+                                 // (the X-cat input-gradient of a layer with an edge update) run the eight-wave 128 x 256 tile from this many
+                                 // rows up, the K-resident panel kernel below (0: never).  Stand-alone, cold, panel / eight waves: one molecule
+                                 // (168 rows) 17.9 / 44.4 us, 32 molecules (5 376 rows) 25.4 / 46.0, 128 molecules (21 504 rows) 65.4 / 54.3;
+                                 // the sizes in between and the C2 step (61.0 -> 53.1 us): profiles/xside_ab.txt
+#endif
 #ifndef GN_F16_BIG8_CAP
 #define GN_F16_BIG8_CAP 256      // persistent workgroups of that kernel (one per CU: eight waves, two per SIMD)
 #endif
