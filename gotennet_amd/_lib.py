@@ -136,6 +136,7 @@ SIGNATURES = {
     "gn_npt_barostat": [_P, _P, _P, _I, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P],
     "gn_npt_rescale": [_P, _P, _P, _P, _P, _I, _I, _P, _P],
     "gn_npt_cell_guard": [_P, _I, _D, _P, _P, _P, _P],
+    "gn_cell_image_ranges": [_P, _I, _D, _I, _P, _P, _P, _P],
     "gn_fire_fmax": [_P, _P, _P, _I, _I, _P, _P],
     "gn_fire_plan": [_P, _P, _P, _P, _I, _I, _D, _D, _I, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "gn_fire_move": [_P, _P, _P, _P, _P, _I, _I, _P, _D, _P, _P],

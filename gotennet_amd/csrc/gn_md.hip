@@ -1,6 +1,7 @@
 // gn_md.hip -- the integrator of a molecular-dynamics step recorded around the energy + force step (gotennet_amd/md.py):
 // velocity-Verlet kick and drift, the Langevin O step with its noise drawn on the device, the kinetic energy, the
-// end-of-step bookkeeping and the barostat (gn_npt_*: the volume move, the rescaling, the internal pressure, the cell guard).
+// end-of-step bookkeeping and the barostat (gn_npt_*: the volume move, the rescaling, the internal pressure, the cell guard;
+// gn_cell_image_ranges: the image ranges of a moved cell, on the guard's arithmetic).
 //
 // state int32 [2]: state[0] is the sticky "the stored neighbour list is stale" word of gn_radius_verify*, state[1] the number
 // of completed steps.  Every kernel here reads state[0] first and does nothing when it is set: a replay on a stale list moves
@@ -221,29 +222,71 @@ __global__ void npt_rescale_kernel(float* __restrict__ pos, float* __restrict__ 
     vel[k] *= inv_s[m];
 }
 
-// Does the moved cell still satisfy what the search parameters of this run assume?  One thread per box, fp64, the formulas
-// of the host's check (graph.cell_widths): w_k = V / |a_i x a_j|; minimum image (img_range == NULL): w_k >= 2 cutoff;
-// else floor(cutoff / w_k + 1/2 + 2^-6) <= R_k.  A volume that is zero or not finite fails either way.
-__global__ void npt_cell_guard_kernel(const float* __restrict__ cell, int n_mol, double cutoff,
-                                      const int* __restrict__ img_range, int* __restrict__ state, int* __restrict__ reason) {
-    if (state[0] != 0) return;
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= n_mol) return;
-    const float* c = cell + 9 * (size_t)m;
+// The perpendicular widths of one cell in fp64 from its fp32 entries, the formulas of the host's check (graph.cell_widths):
+// w[k] = V / |a_i x a_j|, V = |a . (b x c)| returned.  What the guard and the range kernel below both decide from.  A volume
+// that is zero or not finite leaves w unset.
+__device__ __forceinline__ double npt_cell_widths(const float* __restrict__ c, double w[3]) {
     const double a[3] = {c[0], c[1], c[2]}, b[3] = {c[3], c[4], c[5]}, d[3] = {c[6], c[7], c[8]};
     const double f[3][3] = {{b[1] * d[2] - b[2] * d[1], b[2] * d[0] - b[0] * d[2], b[0] * d[1] - b[1] * d[0]},       // b x c
                             {d[1] * a[2] - d[2] * a[1], d[2] * a[0] - d[0] * a[2], d[0] * a[1] - d[1] * a[0]},       // c x a
                             {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]}};      // a x b
     const double vol = fabs((a[0] * f[0][0] + a[1] * f[0][1]) + a[2] * f[0][2]);
+    if (!(isfinite(vol) && vol != 0.0)) return vol;
+    for (int k = 0; k < 3; ++k) w[k] = vol / sqrt((f[k][0] * f[k][0] + f[k][1] * f[k][1]) + f[k][2] * f[k][2]);
+    return vol;
+}
+
+// The image range a width asks for, floor(cutoff / w + 1/2 + 2^-6) (graph.image_ranges), as a double: the caller compares
+__device__ __forceinline__ double npt_image_range(double cutoff, double w) { return floor(cutoff / w + 0.5 + 0.015625); }
+
+// Does the moved cell still satisfy what the search parameters of this run assume?  One thread per box, fp64:
+// minimum image (img_range == NULL): w_k >= 2 cutoff; else floor(cutoff / w_k + 1/2 + 2^-6) <= R_k.  A volume that is zero
+// or not finite fails either way.
+__global__ void npt_cell_guard_kernel(const float* __restrict__ cell, int n_mol, double cutoff,
+                                      const int* __restrict__ img_range, int* __restrict__ state, int* __restrict__ reason) {
+    if (state[0] != 0) return;
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_mol) return;
+    double w[3];
+    const double vol = npt_cell_widths(cell + 9 * (size_t)m, w);
     bool ok = isfinite(vol) && vol != 0.0;
     for (int k = 0; k < 3 && ok; ++k) {
-        const double w = vol / sqrt((f[k][0] * f[k][0] + f[k][1] * f[k][1]) + f[k][2] * f[k][2]);
-        if (img_range == nullptr) ok = w >= 2.0 * cutoff;
-        else ok = isfinite(w) && w > 0.0 && floor(cutoff / w + 0.5 + 0.015625) <= (double)img_range[3 * m + k];
+        if (img_range == nullptr) ok = w[k] >= 2.0 * cutoff;
+        else ok = isfinite(w[k]) && w[k] > 0.0 && npt_image_range(cutoff, w[k]) <= (double)img_range[3 * m + k];
     }
     if (!ok) {
         reason[m] = 1;
         state[0] = 1;
+    }
+}
+
+// The image ranges of the moved cell, for a search that is rebuilt inside the step: ONE workgroup, a thread per box (strided
+// beyond 1024 boxes), the guard's arithmetic.  Every thread reads the sticky word before the barrier and nobody writes it
+// before, so a launch that starts frozen writes nothing and a launch that starts clear treats every box alike, whatever
+// another box of the same launch decides.  img_range[m, k] = floor(cutoff / w_k + 1/2 + 2^-6); a box whose volume is zero or
+// not finite, or that asks for more than max_range images on some axis, keeps its row and stores reason 1 and the word.
+__global__ __launch_bounds__(1024) void cell_image_ranges_kernel(const float* __restrict__ cell, int n_mol, double cutoff,
+                                                                int max_range, int* __restrict__ img_range,
+                                                                int* __restrict__ state, int* __restrict__ reason) {
+    const int frozen = state[0];
+    __syncthreads();
+    if (frozen != 0) return;                           // (uniform: one word, read by all before anybody stores it)
+    for (int m = threadIdx.x; m < n_mol; m += 1024) {
+        double w[3];
+        const double vol = npt_cell_widths(cell + 9 * (size_t)m, w);
+        bool ok = isfinite(vol) && vol != 0.0;
+        int r[3] = {0, 0, 0};
+        for (int k = 0; k < 3 && ok; ++k) {
+            const double rk = isfinite(w[k]) && w[k] > 0.0 ? npt_image_range(cutoff, w[k]) : -1.0;
+            ok = rk >= 0.0 && rk <= (double)max_range;
+            r[k] = ok ? (int)rk : 0;
+        }
+        if (ok) {
+            for (int k = 0; k < 3; ++k) img_range[3 * (size_t)m + k] = r[k];
+        } else {
+            reason[m] = 1;
+            state[0] = 1;
+        }
     }
 }
 
@@ -357,6 +400,18 @@ extern "C" int gn_npt_cell_guard(const float* cell, int n_mol, double cutoff, co
     if (!npt_count_ok(n_mol) || !state || !(cutoff > 0.0) || (n_mol > 0 && (!cell || !reason))) return GN_ERR_BAD_ARG;
     if (n_mol == 0) return GN_OK;
     hipLaunchKernelGGL(gn::npt_cell_guard_kernel, dim3((n_mol + 63) / 64), dim3(64), 0, (hipStream_t)stream, cell, n_mol, cutoff,
+                       img_range, state, reason);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" int gn_cell_image_ranges(const float* cell, int n_mol, double cutoff, int max_range, int* img_range, int* state,
+                                   int* reason, void* stream) {
+    if (!npt_count_ok(n_mol) || !state || !(cutoff > 0.0) || max_range < 0 || max_range > GN_PBC_MAX_IMAGE_RANGE ||
+        (n_mol > 0 && (!cell || !img_range || !reason)))
+        return GN_ERR_BAD_ARG;
+    if (n_mol == 0) return GN_OK;
+    hipLaunchKernelGGL(gn::cell_image_ranges_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, cell, n_mol, cutoff, max_range,
                        img_range, state, reason);
     GN_LAUNCH_CHECK();
     return GN_OK;

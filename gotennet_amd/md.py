@@ -21,7 +21,12 @@ the list inside the step: the search's own count and fill kernels around a devic
 unused tail belongs to dummy atoms (``pipeline.RebuiltStep``, ``graph.PaddedLayout``).  The list is never stale, so there is no
 verify kernel, no repair and no second recording; the sticky word is set only by the overflow guard of gn_padded_tail, and the
 host reads the state every ``check_every`` replays for the step counter.  ``captured=False`` launches the same chain eagerly on
-the same padded buffers.  The cell is fixed in this mode.
+the same padded buffers.  With a barostat the step is ``RebuiltStep(cell_moves=True)`` (``images`` "all" or "auto"; "minimum" is
+refused): the braces above read {barostat -> rescale -> cell inverse}, the driver's own inverse and volume by a gn_cell_prepare
+launch of its own, and the rebuilt list starts gn_cell_prepare -> gn_cell_image_ranges -> count, so the ranges of the search are
+those of the moved cell in every step and nothing is re-recorded when they change.  gn_cell_image_ranges takes the guard's
+place: a cell without volume or narrower than its bound (R > 3, a little below ``cutoff / 3``) stores reason 1 and the sticky
+word, and ``run`` raises what ``graph.image_ranges`` raises on the reported cell.
 
 Constant pressure (``barostat=``): isotropic stochastic cell rescaling (Bernetti and Bussi, J. Chem. Phys. 153, 114107, 2020)
 written in eps = ln V.  Per box and step::
@@ -128,21 +133,23 @@ def barostat_parameters(barostat: dict, thermostat: Optional[dict], cell) -> dic
 REBUILD_MODES = ("host", "device")
 
 
-def check_rebuild(rebuild, barostat=None) -> None:
-    """``rebuild=`` of ``MDRun`` / ``relax.Relax``, or ``ValueError``: a known mode, and no barostat in device mode (a moving cell
-    can outgrow the image ranges of the search, which is a host decision)."""
+def check_rebuild(rebuild, barostat=None, images="minimum") -> None:
+    """``rebuild=`` of ``MDRun`` / ``relax.Relax``, or ``ValueError``: a known mode, and in device mode no barostat with
+    ``images="minimum"`` (the multi-image search recomputes its ranges on the device; whether a moved cell is still a
+    minimum-image cell is a host decision)."""
     if rebuild not in REBUILD_MODES:
         raise ValueError(f"rebuild must be one of {REBUILD_MODES}, got {rebuild!r}")
-    if rebuild == "device" and barostat is not None:
-        raise ValueError('rebuild="device" with a barostat: the device rebuild runs on a fixed cell (a moving cell can outgrow '
-                         'the image ranges, which the host decides); use rebuild="host"')
+    if rebuild == "device" and barostat is not None and images == "minimum":
+        raise ValueError('rebuild="device" with a barostat and images="minimum": a cell that shrinks below 2 * cutoff is the '
+                         'host\'s decision; images="all" (or "auto") runs on the device, its image ranges recomputed in every '
+                         'step, or use rebuild="host"')
 
 
 def validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images="minimum", check_every=1, log_len=1,
              rebuild="host", barostat=None):
     """Everything ``MDRun`` refuses, before any launch -> (mass table fp32 on the CPU, ``graph.resolve_images``' result or None).
     Raises ``ValueError``.  Reads ``z`` (and ``cell``) on the host."""
-    check_rebuild(rebuild, barostat)
+    check_rebuild(rebuild, barostat, images)
     if not (math.isfinite(float(dt)) and float(dt) > 0):
         raise ValueError(f"dt must be positive and finite, got {dt}")
     if not (math.isfinite(float(force_scale)) and float(force_scale) > 0):
@@ -213,12 +220,16 @@ class _RecordedStep(CapturedStep):
 class _RebuiltRecordedStep(RebuiltStep):
     """``rebuild="device"``: ``RebuiltStep`` with the integrator around its body -- ``_pre`` -> the rebuild -> model -> ``_post`` --
     recorded (``capture``) or launched eagerly on the same padded buffers.  No verify kernel: the list is never stale.  The
-    driver's sticky word is the one gn_padded_tail sets; the driver is held weakly, as in ``_RecordedStep``."""
+    driver's sticky word is the one gn_padded_tail sets; the driver is held weakly, as in ``_RecordedStep``.  A driver with a
+    barostat gets the moving-cell form of the step: gn_cell_image_ranges, inside the rebuild, writes the driver's sticky word
+    and its ``_reason``."""
 
     def __init__(self, md: "_ListDriver", capture: bool):
         self.md = weakref.proxy(md)
+        moves = getattr(md, "_baro", None) is not None
         super().__init__(md.ef, md._z, md._batch, md.n_mol, max_num_neighbors=md.max_num_neighbors, cell=md._cell,
-                         images=md.images, capture=capture, state=md._state)
+                         images=md.images, capture=capture, state=md._state, cell_moves=moves,
+                         reason=md._reason if moves else None)
 
     def _body(self):
         self.md._pre(self.pos, self.cell)
@@ -390,7 +401,8 @@ class _ListDriver(metaclass=_RebuildOption):
     def _run_device(self, n: int):
         """``rebuild="device"``: nothing is verified, repaired or re-recorded.  The host reads the device state after every
         ``check_every`` steps (after the first replay of the graph, and at the end) for the step counter, ``_looked`` and the
-        overflow guard of gn_padded_tail only."""
+        sticky word: a driver's own reasons (``_guarded``: the barostat's) raise first, else it is the overflow guard of
+        gn_padded_tail."""
         target = self._done + n
         while self._done < target:
             burst = 1 if self._fresh else min(self.check_every, target - self._done)
@@ -402,6 +414,7 @@ class _ListDriver(metaclass=_RebuildOption):
             self._fresh = False
             overflow, self._done = self._state.tolist()          # (the synchronisation)
             if overflow:
+                self._guarded()                                  # (a driver's own reasons first: they raise)
                 raise RuntimeError(f"the neighbour search found {self.edge_count} edges, outside the padded layout's bound "
                                    f"[{self.N}, {self._step.layout.e_bound}]: the run stops at step {self._done}")
             if self._looked():
@@ -444,7 +457,9 @@ class MDRun(_ListDriver):
     recording; ``rebuilds`` stays 0 and ``edge_count`` reports the current number of real edges.  For systems whose list changes
     often (a host rebuild costs about ten eager steps).  ``captured=False, rebuild="device"`` launches the same chain eagerly on
     the same padded buffers and agrees with the recorded one bit for bit; in the "f32" and "split" arithmetics both are the
-    ``rebuild="host"`` trajectory, bit for bit.  The cell is fixed: ``barostat=`` is refused in this mode.
+    ``rebuild="host"`` trajectory, bit for bit.  With ``barostat=`` it needs ``images="all"`` or ``"auto"``: the step then always
+    runs the multi-image search and recomputes its image ranges from the moved cell on the device (module docstring), so a
+    constant-pressure run replays one graph from start to end; ``images="minimum"`` with a barostat is refused in this mode.
 
     ``barostat``: None (the cell is fixed: the launches and the bits of a run without this argument) or
     ``dict(pressure=, tau=, compressibility=, kT=None, key=None, max_step=0.05)``: isotropic stochastic cell rescaling on the
@@ -460,7 +475,7 @@ class MDRun(_ListDriver):
     Refused with ``ValueError`` before any launch: dt <= 0, a negative or missing mass, kT < 0, gamma < 0, a cell that
     ``graph.resolve_images`` refuses, ``pos`` or ``cell`` requiring grad; a barostat without a cell, with entries missing, with
     tau, compressibility or max_step not positive and finite, a non-finite pressure, kT < 0, or kT > 0 without a key; an
-    unknown ``rebuild``, or ``rebuild="device"`` with a barostat."""
+    unknown ``rebuild``, or ``rebuild="device"`` with a barostat and ``images="minimum"``."""
 
     def __init__(self, ef: EnergyForces, z: torch.Tensor, pos: torch.Tensor, batch: torch.Tensor, n_mol: int, dt: float,
                  masses=None, force_scale: float = 1.0, vel: Optional[torch.Tensor] = None,
@@ -535,9 +550,10 @@ class MDRun(_ListDriver):
         if b is not None:
             call("gn_npt_rescale", ptr(pos), ptr(self._vel), ptr(self._batch), ptr(self._s), ptr(self._inv_s), self.N, self.n_mol,
                  ptr(self._state), engine._stream())
-            graph.cell_prepare(cell, self._inv_cell, self._volume)
-            call("gn_npt_cell_guard", ptr(cell), self.n_mol, self.cutoff, ptr(self._ranges), ptr(self._state), ptr(self._reason),
-                 engine._stream())
+            graph.cell_prepare(cell, self._inv_cell, self._volume)     # (the driver's own volume: the pressure's and the next move's)
+            if self.rebuild != "device":   # device mode: gn_cell_image_ranges inside the step takes the guard's place
+                call("gn_npt_cell_guard", ptr(cell), self.n_mol, self.cutoff, ptr(self._ranges), ptr(self._state),
+                     ptr(self._reason), engine._stream())
 
     def _post(self, energy, forces, stress=None):
         self._kick(forces)
@@ -550,13 +566,18 @@ class MDRun(_ListDriver):
     def _guarded(self):
         """The sticky word is set: was it the barostat?  Reason 2 (a move beyond ``max_step``) ends the run; reason 1 (the cell
         outgrew the search parameters) gets new ones from ``graph.resolve_images`` on the current cell, or what that raises.
-        The caller repairs the list next."""
+        The caller repairs the list next.  Device mode repairs nothing: reason 1 is gn_cell_image_ranges' refusal and raises
+        what ``graph.image_ranges`` raises on the reported cell."""
         if self._baro is None:
             return
         reason = self._reason.tolist()
         if 2 in reason:
             raise RuntimeError(f"barostat: box {reason.index(2)} asks for a volume move |d ln V| that is not finite or exceeds "
                                f"max_step = {self._baro['max_step']} in step {self._done + 1}; the run stops at step {self._done}")
+        if 1 in reason and self.rebuild == "device":            # gn_cell_image_ranges refused the moved cell: the host's words
+            graph.image_ranges(self._cell, self.cutoff)
+            raise RuntimeError(f"barostat: the device refused the image ranges of box {reason.index(1)} in step {self._done + 1}, "
+                               f"but graph.image_ranges accepts the reported cell; the run stops at step {self._done}")
         if 1 in reason:
             ranges = graph.resolve_images(self._cell, self.cutoff, self.images)
             self._ranges = None if ranges is None else ranges.expand(self.n_mol, 3).contiguous().to(self._cell.device)

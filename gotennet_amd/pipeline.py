@@ -2,7 +2,11 @@
 head gradient -> hand-written backward -> force scatter, all through the C ABI with no
 autograd graph and no host synchronisation (hipGraph-capturable).  This is the path
 bench.py times; the autograd.Function wrappers in gotennet.py expose the same kernels to
-reference-style callers (GotenModel / torch.autograd.grad)."""
+reference-style callers (GotenModel / torch.autograd.grad).
+
+``CapturedStep`` records that step on a fixed edge list into one hipGraph; ``RebuiltStep`` records it behind a rebuild of
+the list on the device, for a fixed cell or (``cell_moves=True``) for one that moves between the replays, its image ranges
+recomputed inside the chain by gn_cell_image_ranges."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -10,6 +14,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import engine, graph
+from ._lib import call, ptr
 from .gotennet import GotenNet
 from .outputs import Atomwise, molecule_ptr
 
@@ -434,9 +439,21 @@ class RebuiltStep:
     ``EnergyForces`` on the unpadded list; "f16x2" shares block exponents between neighbouring rows and agrees to its usual
     1e-6 relative.  ``step.edge_index`` / ``step.edge_shift`` are the capacity-sized buffers.
 
-    Periodic steps (``cell``, ``images`` as ``graph.distance_pbc``): the cell is FIXED -- the image ranges of the search are a
-    host decision -- and a cell passed per call is refused.  The dummy molecule gets the identity cell (volume 1, zero virial);
+    Periodic steps (``cell``, ``images`` as ``graph.distance_pbc``): the cell is FIXED unless ``cell_moves`` is set (below) -- the
+    choice between the minimum-image and the multi-image kernels is a host decision -- and a cell passed per call is
+    refused.  The dummy molecule gets the identity cell (volume 1, zero virial);
     ``step.cell`` is the [n_mol, 3, 3] view of the real boxes.
+
+    ``cell_moves=True`` (opt-in; needs ``cell`` and ``images`` "all" or "auto"): the cell may change between two calls --
+    ``step.set_cell(cell)``, or a kernel that writes ``step.cell`` (the barostat of ``md.MDRun``).  The step then always runs the
+    multi-image kernels on a list of capacity sum_m n_m * max_num_neighbors, which holds for any image range, and owns the
+    range array (int32 [n_mol, 3], initialised from ``graph.image_ranges``; all zero on a wide cell, where the multi-image walk
+    is the minimum-image walk candidate for candidate).  The chain starts gn_cell_prepare -> gn_cell_image_ranges -> count: the
+    inverse and the ranges belong to the current cell before the search reads them, and no second gn_cell_prepare follows
+    the list.  A cell the range kernel refuses (no volume, or R > 3: a width below ``cutoff / 3.48``) keeps the old ranges, stores
+    1 in ``step.reason`` [n_mol] (or the caller's ``reason`` tensor) and sets the sticky ``state`` word; the step still runs, and
+    what it returns for such a cell means nothing.  A cell per call stays refused.  Without the keyword the step launches
+    what it always launched, in the same order.
 
     ``capture=False``: the same launches on the same buffers, eagerly in every call (the reference of the recorded mode).
     ``state``: an int32 tensor whose first word gn_padded_tail sets when the edge count leaves the layout's bound (sticky;
@@ -444,13 +461,22 @@ class RebuiltStep:
 
     def __init__(self, ef: EnergyForces, z: torch.Tensor, batch: torch.Tensor, n_mol: int, max_num_neighbors: int = 32,
                  cell: Optional[torch.Tensor] = None, images: str = "minimum", warmup: int = 2, capture: bool = True,
-                 state: Optional[torch.Tensor] = None):
+                 state: Optional[torch.Tensor] = None, cell_moves: bool = False, reason: Optional[torch.Tensor] = None):
         rep, head = ef.rep, ef.head
         if cell is not None and cell.requires_grad:          # before any launch
             raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
         if images not in graph.IMAGE_MODES:
             raise ValueError(f"images must be one of {graph.IMAGE_MODES}, got {images!r}")
+        self.cell_moves = bool(cell_moves)
+        if self.cell_moves and cell is None:
+            raise ValueError("RebuiltStep: cell_moves=True needs a cell")
+        if self.cell_moves and images == "minimum":
+            raise ValueError('RebuiltStep: cell_moves=True with images="minimum": whether a moved cell is still at least '
+                             '2 * cutoff wide is the host\'s decision; images="all" (or "auto") recomputes the image ranges on '
+                             'the device')
         ranges = graph.resolve_images(cell, float(rep.cutoff), images) if cell is not None else None
+        if self.cell_moves and ranges is None:                # "auto" on a wide cell: the multi-image kernels all the same
+            ranges = graph.image_ranges(cell.detach().cpu(), float(rep.cutoff))
         dev = z.device
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
         self.layout = lay = graph.PaddedLayout(batch, n_mol, max_num_neighbors, z=z, periodic_images=ranges is not None).to(dev)
@@ -474,6 +500,8 @@ class RebuiltStep:
             self.cell = self._cell_all[:self.n_mol]                     # a view: the driver's [n_mol, 3, 3] cell
             self.inv_cell, self.volume = graph.cell_prepare(self._cell_all)     # (the search reads the inverse before step 6)
             self._ranges = None if ranges is None else ranges.expand(self.n_mol, 3).contiguous().to(dev)
+        #: ``cell_moves``: why a box set the sticky word (1: gn_cell_image_ranges refused its cell), int32 [n_mol]
+        self.reason = (torch.zeros(self.n_mol, **i32) if reason is None else reason) if self.cell_moves else None
         self.g = engine.Graph(self.cfg, self.pw, lay.n_atoms, self.edge_index, self_images=cell is not None)
         self.energy = self.forces = self.stress = self.graph = None
         if not capture:
@@ -506,8 +534,12 @@ class RebuiltStep:
 
     def _body(self):
         cfg, pw, g, n_all = self.cfg, self.pw, self.g, self.n_mol + 1
+        if self.cell_moves:        # the inverse and the ranges of the CURRENT cell, before the count reads them
+            graph.cell_prepare(self._cell_all, self.inv_cell, self.volume)
+            call("gn_cell_image_ranges", ptr(self.cell), self.n_mol, self.cutoff, graph.MAX_IMAGE_RANGE, ptr(self._ranges),
+                 ptr(self.state), ptr(self.reason), engine._stream())
         self.rebuild()
-        if self.cell is not None:
+        if self.cell is not None and not self.cell_moves:
             graph.cell_prepare(self._cell_all, self.inv_cell, self.volume)
         g.set_geometry(self.edge_diff, self.edge_vec)     # (the fill's unshifted() / shifted(): the bits set_positions would give)
         h, X, tape = engine.forward(cfg, pw, self.z32, g, save=True)
@@ -518,6 +550,17 @@ class RebuiltStep:
         if self.cell is None:
             return e[:self.n_mol], f[:self.N]
         return e[:self.n_mol], f[:self.N], engine.virial(g, g_vec, g_diff, self.mol_ptr, n_all, self.volume)[:self.n_mol]
+
+    @torch.no_grad()
+    def set_cell(self, cell: torch.Tensor) -> None:
+        """``cell_moves=True``: copy a new cell (fp32 [n_mol, 3, 3] or [3, 3]) into the static buffer; the next call prepares it,
+        recomputes its image ranges and searches in it.  Not checked on the host: a cell the range kernel refuses sets the
+        sticky ``state`` word and ``reason`` of its box."""
+        if cell.requires_grad:                                # before any launch
+            raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
+        if not self.cell_moves:
+            raise ValueError("RebuiltStep.set_cell: this step was built for a fixed cell; pass cell_moves=True")
+        self.cell.copy_(graph.broadcast_cell(cell.to(self.cell.device), self.n_mol))
 
     @torch.no_grad()
     def __call__(self, pos: torch.Tensor, cell: Optional[torch.Tensor] = None):

@@ -686,6 +686,15 @@ int gn_npt_rescale(float* pos, float* vel, const int64_t* batch, const float* s,
  * reason[m] = 1 and state[0] = 1. */
 int gn_npt_cell_guard(const float* cell, int n_mol, double cutoff, const int* img_range, int* state, int* reason,
                       void* stream);
+/* gn_cell_image_ranges, one workgroup, a thread per box, fp64, the guard's widths: the image ranges of the moved cell for a
+ * search that is rebuilt inside the step (pipeline.RebuiltStep(cell_moves=True)), launched behind gn_cell_prepare and in
+ * front of gn_radius_count_pbc_images.  img_range[m, k] = floor(cutoff / w_k + 1/2 + 2^-6) (graph.image_ranges' rule).  A box
+ * whose volume is zero or not finite, or with some R_k > max_range (at most GN_PBC_MAX_IMAGE_RANGE), keeps its row of
+ * img_range and stores reason[m] = 1 and state[0] = 1; the other boxes of that launch are written.  state[0] != 0 on
+ * entry: nothing is written.  (R_k <= 3 holds down to w_k = cutoff / (3.5 - 2^-6), a little below the cutoff / 3 at which the
+ * host's graph.image_ranges refuses: the range is what the search needs, the host's bound is the round one.) */
+int gn_cell_image_ranges(const float* cell, int n_mol, double cutoff, int max_range, int* img_range, int* state,
+                        int* reason, void* stream);
 
 /* ---- FIRE relaxation around a recorded energy + force step (gotennet_amd/relax.py; Bitzek et al., PRL 97, 170201, the
  * variant ASE's FIRE implements, unit masses) ----------------------------------------------------------------------
