@@ -154,11 +154,19 @@ def box_arrays(cell: torch.Tensor, ranges: Optional[torch.Tensor], n_mol: int, d
 IMAGE_MODES = ("minimum", "auto", "all")
 
 
+def check_periodic_args(cell: Optional[torch.Tensor] = None, images: str = "minimum") -> None:
+    """The two refusals every periodic entry point of the step classes and the drivers makes before any launch, stated once:
+    a ``cell`` that requires grad, then an unknown ``images``.  Raises ``ValueError``; reads nothing on the device."""
+    if cell is not None and cell.requires_grad:
+        raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
+    if images not in IMAGE_MODES:
+        raise ValueError(f"images must be one of {IMAGE_MODES}, got {images!r}")
+
+
 def resolve_images(cell: torch.Tensor, cutoff: float, images: str) -> Optional[torch.Tensor]:
     """The cell check of ``distance_pbc(images=)``, from ONE host read of ``cell`` -> None (the minimum-image kernels: every
     box passed ``check_cell``) or the ``image_ranges`` array (the multi-image kernels).  Raises what those checks raise."""
-    if images not in IMAGE_MODES:
-        raise ValueError(f"images must be one of {IMAGE_MODES}, got {images!r}")
+    check_periodic_args(images=images)
     cell_host = cell.detach().cpu()
     if images == "all":
         return image_ranges(cell_host, cutoff)

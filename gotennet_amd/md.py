@@ -64,7 +64,7 @@ import torch
 from . import engine, graph
 from ._lib import call, ptr
 from .outputs import _ATOMIC_MASS, molecule_ptr
-from .pipeline import CapturedStep, EnergyForces, RebuiltStep
+from .pipeline import CapturedStep, EnergyForces, RebuiltStep, energy_forces
 
 #: ``force_scale`` turns force / mass into an acceleration in the caller's length and time units:
 #: a = force_scale * F / m.  1 when the units are consistent already (the default).  Two common sets, masses in amu,
@@ -175,10 +175,7 @@ def validate(z, pos, dt, masses, force_scale, thermostat, cell, cutoff, images="
         barostat_parameters(barostat, thermostat, cell)
     if pos.requires_grad:
         raise ValueError("pos requires grad: the driver integrates plain tensors")
-    if cell is not None and cell.requires_grad:
-        raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
-    if images not in graph.IMAGE_MODES:
-        raise ValueError(f"images must be one of {graph.IMAGE_MODES}, got {images!r}")
+    graph.check_periodic_args(cell, images)
     ranges = graph.resolve_images(cell, float(cutoff), images) if cell is not None else None
     return table, ranges
 
@@ -220,13 +217,13 @@ class _RecordedStep(CapturedStep):
 class _RebuiltRecordedStep(RebuiltStep):
     """``rebuild="device"``: ``RebuiltStep`` with the integrator around its body -- ``_pre`` -> the rebuild -> model -> ``_post`` --
     recorded (``capture``) or launched eagerly on the same padded buffers.  No verify kernel: the list is never stale.  The
-    driver's sticky word is the one gn_padded_tail sets; the driver is held weakly, as in ``_RecordedStep``.  A driver with a
-    barostat gets the moving-cell form of the step: gn_cell_image_ranges, inside the rebuild, writes the driver's sticky word
-    and its ``_reason``."""
+    driver's sticky word is the one gn_padded_tail sets; the driver is held weakly, as in ``_RecordedStep``.  A driver whose
+    cell moves (``_ListDriver._cell_moves``) gets the moving-cell form of the step: gn_cell_image_ranges, inside the rebuild,
+    writes the driver's sticky word and its ``_reason``."""
 
     def __init__(self, md: "_ListDriver", capture: bool):
         self.md = weakref.proxy(md)
-        moves = getattr(md, "_baro", None) is not None
+        moves = md._cell_moves
         super().__init__(md.ef, md._z, md._batch, md.n_mol, max_num_neighbors=md.max_num_neighbors, cell=md._cell,
                          images=md.images, capture=capture, state=md._state, cell_moves=moves,
                          reason=md._reason if moves else None)
@@ -239,22 +236,32 @@ class _RebuiltRecordedStep(RebuiltStep):
 
 
 class _EagerStep:
-    """What ``CapturedStep._body`` reads, for a list that is rebuilt in every step: the same body, launched eagerly."""
-    _body = CapturedStep._body
+    """``rebuild="host"``, ``captured=False``: the holder of the ``engine.Graph`` of the current list -- a new one for the list of
+    every step (``set_list``) -- and of the position buffer the driver integrates.  ``model`` launches what ``CapturedStep``
+    records, [gn_cell_prepare ->] edge vectors -> geometry -> ``pipeline.energy_forces``, eagerly."""
 
-    def __init__(self, md: "MDRun"):
-        rep = md.ef.rep
-        self.cfg, self.pw, self.head = rep.config(), rep.packed_weights(), md.ef.head
-        self.z32, self.mol_ptr, self.N, self.n_mol, self.pos = md._z32, md._mol_ptr, md.N, md.n_mol, md._pos
-        self.cell, self.batch, self.g = md._cell, md._batch, None
+    def __init__(self, md: "_ListDriver", edge_index: torch.Tensor, edge_shift: Optional[torch.Tensor]):
+        rep, dev = md.ef.rep, md._z32.device
+        self.md, self.cfg, self.pw = weakref.proxy(md), rep.config(), rep.packed_weights()
+        self.pos, self.cell = torch.zeros((md.N, 3), dtype=torch.float32, device=dev), md._cell
+        self.inv_cell = self.volume = None
         if self.cell is not None:
-            self.inv_cell, self.volume = torch.empty_like(self.cell), torch.empty(md.n_mol, dtype=torch.float32, device=self.cell.device)
+            self.inv_cell, self.volume = torch.empty_like(self.cell), torch.empty(md.n_mol, dtype=torch.float32, device=dev)
+        self.set_list(edge_index, edge_shift)
 
     def set_list(self, edge_index, edge_shift):
-        self.g = engine.Graph(self.cfg, self.pw, self.N, edge_index.contiguous(), self_images=self.cell is not None)
+        self.g = engine.Graph(self.cfg, self.pw, self.md.N, edge_index.contiguous(), self_images=self.cell is not None)
         if self.cell is not None:
-            self.g.set_periodic(edge_shift, self.batch, self.cell)
+            self.g.set_periodic(edge_shift, self.md._batch, self.cell)
         self.g.csc()
+
+    def model(self):
+        md = self.md
+        if self.cell is not None:
+            graph.cell_prepare(self.cell, self.inv_cell, self.volume)
+        self.g.set_positions(self.pos, self.cell)
+        return energy_forces(cfg=self.cfg, pw=self.pw, head=md.ef.head, z32=md._z32, g=self.g, mol_ptr=md._mol_ptr,
+                             n_mol=md.n_mol, volume=self.volume)
 
 
 class _RebuildOption(type):
@@ -271,19 +278,25 @@ class _RebuildOption(type):
 
 
 class _ListDriver(metaclass=_RebuildOption):
-    """What ``MDRun`` and ``relax.Relax`` share, once: the neighbour search, the device check of the stored list, the
-    record / repair / replay loop and the handling of the sticky word.  A driver supplies ``_pre(pos, cell)`` (everything before
-    the neighbour list) and ``_post(energy, forces[, stress])`` (everything after the model) -- the protocol ``_RecordedStep`` and
-    ``_EagerStep`` talk to -- and may override ``_guarded`` (the sticky word is set: was it something other than the list?),
-    ``_after_pre`` (eager mode, between ``_pre`` and the search) and ``_looked`` (the host has just read the device state: True
-    ends ``run`` early)."""
+    """What ``MDRun`` and ``relax.Relax`` share, once: the kept buffers of the last completed step and their properties, the
+    neighbour search, the device check of the stored list, the record / repair / replay loop and the handling of the sticky
+    word.  A driver supplies ``_pre(pos, cell)`` (everything before the neighbour list) and ``_post(energy, forces[, stress])``
+    (everything after the model) -- the protocol the three step classes above talk to -- and may override ``_cell_moves``,
+    ``_guarded`` (the sticky word is set: was it something other than the list?), ``_after_pre`` (eager mode, between ``_pre`` and
+    the search) and ``_looked`` (the host has just read the device state: True ends ``run`` early).
 
-    def _setup(self, ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured):
+    The three modes differ in the step they build (``_record``), in what advances one step (``_advance``) and in what a set
+    sticky word means (``_stuck``); ``run`` is written once."""
+
+    #: the cell changes between two steps (a barostat): the device-rebuilt step recomputes its image ranges in every step
+    _cell_moves = False
+
+    def _setup(self, ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured, log_len, vel=None):
         dev = pos.device
-        i32 = dict(dtype=torch.int32, device=dev)
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
         self.ef, self.n_mol, self.N, self.images = ef, int(n_mol), pos.shape[0], images
         self.cutoff, self.max_num_neighbors = float(ef.rep.cutoff), int(max_num_neighbors)
-        self.captured, self.check_every = bool(captured), int(check_every)
+        self.captured, self.check_every, self.log_len = bool(captured), int(check_every), int(log_len)
         self._z, self._z32 = z, z.to(torch.int32).contiguous()
         self._batch = batch.to(torch.int64).contiguous()
         self._mol_ptr = molecule_ptr(self._batch, self.n_mol)
@@ -293,31 +306,24 @@ class _ListDriver(metaclass=_RebuildOption):
         self._state = torch.zeros(2, **i32)                       # {stale list (sticky), completed steps}
         self._row_flag, self._changed = torch.zeros(self.N, **i32), torch.zeros(self.n_mol, **i32)
         self._done, self.rebuilds, self._fresh = 0, 0, False
+        # every buffer of the recorded chain is made and initialised here, by torch, never inside the recording
+        self._vel = torch.zeros((self.N, 3), **f32) if vel is None else vel.detach().to(**f32).clone().contiguous()
+        self._f = torch.empty((self.N, 3), **f32)                 # forces of the last completed step: what the next one starts from
+        self._e = torch.empty(self.n_mol, **f32)
+        self._stress = torch.empty((self.n_mol, 3, 3), **f32) if cell is not None else None
+        self._log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
 
     def _start(self, start):
-        """The first list and the first model evaluation at ``start`` -> (energy, forces[, stress]) of the step's own buffers."""
-        if self.rebuild == "device":
-            # the step owns the padded buffers; recorded or not, the chain is the same.  The sticky word is held at 1 while
-            # the recording's warm-up runs (they advance nothing), as in ``_record``
-            self._state[:1].fill_(1)
-            self._step = _RebuiltRecordedStep(self, capture=self.captured)
-            self._step.pos.copy_(start)
-            self._pos, self._cell, self._fresh = self._step.pos, self._step.cell, self.captured
-            self._state[:1].zero_()
-            with torch.no_grad():
-                return self._step.model()
-        lst = self._list(start)
-        if self.captured:
-            self._step, self._pos = None, start
-            self._record(lst)
-            self._state[:1].zero_()
-            with torch.no_grad():
-                return self._step.model()
-        self._pos = start.clone()
-        self._eager, self._lst = _EagerStep(self), lst
-        self._eager.set_list(*lst)
+        """The first step object and the first model evaluation, at ``start``: its forces, energies and stress are the kept
+        ones of step 0."""
+        self._record(start)
+        self._state[:1].zero_()
         with torch.no_grad():
-            return self._eager._body()
+            out = self._step.model()
+        self._f.copy_(out[1])
+        self._e.copy_(out[0].reshape(-1))
+        if self._stress is not None:
+            self._stress.copy_(out[2])
 
     def _list(self, pos):
         """(edge_index, edge_shift or None) of ``pos``: the project's own search (one host read of the edge count)."""
@@ -332,16 +338,19 @@ class _ListDriver(metaclass=_RebuildOption):
                           self._row_flag, self._changed, self._state, shift=g.shift, cell=cell,
                           inv_cell=self._inv_cell, image_range=self._ranges)
 
-    def _record(self, lst):
-        """Record the step on the list ``lst`` and move the positions into its static buffer; the recording's clone of the
-        current cell becomes the driver's cell.  The sticky word is held at 1 meanwhile (the recording's warm-up runs advance
-        nothing) and LEFT at 1: the caller clears it."""
+    def _record(self, pos):
+        """Build the mode's step at ``pos`` -- device list: the step that owns the padded buffers, recorded or not; host list: the
+        search, then the recording on that list or the eager holder of it -- and move ``pos`` into its buffer; the step's position
+        buffer and its cell (a recording's clone of the current one) become the driver's.  The sticky word is held at 1 meanwhile
+        (a recording's warm-up runs advance nothing) and LEFT at 1: the caller clears it."""
         self._state[:1].fill_(1)
-        pos = self._pos
-        self._step = _RecordedStep(self, lst[0], lst[1])
+        if self.rebuild == "device":
+            self._step = _RebuiltRecordedStep(self, capture=self.captured)
+        else:
+            self._lst = self._list(pos)
+            self._step = (_RecordedStep if self.captured else _EagerStep)(self, *self._lst)
         self._step.pos.copy_(pos)
-        self._pos, self._cell = self._step.pos, self._step.cell
-        self._fresh = True
+        self._pos, self._cell, self._fresh = self._step.pos, self._step.cell, self.captured
 
     def _guarded(self):
         pass
@@ -355,68 +364,59 @@ class _ListDriver(metaclass=_RebuildOption):
     def _repair(self):
         """The sticky word is set: the state is the one after the move (MD: the drift and the cell move) of the first incomplete
         step.  New list there, new graph (the old one is dropped first: one alive at a time), then the rest of that step eagerly."""
-        lst = self._list(self._pos)
         torch.cuda.synchronize()
-        self._step = None
-        self._record(lst)
+        pos, self._step = self._pos, None
+        self._record(pos)
         self._state[:1].zero_()
         self._post(*self._step.model())
         self.rebuilds += 1
         self._done += 1
 
+    def _advance(self):
+        """One step of the mode: a replay of the recording, the device-list chain launched eagerly, or (host list, eager) the
+        chain around a new search."""
+        if self.captured:
+            self._step.graph.replay()
+        elif self.rebuild == "device":
+            self._step._body()
+        else:
+            self._pre(self._pos, self._cell)
+            self._after_pre()
+            lst = self._list(self._pos)
+            if not (torch.equal(lst[0], self._lst[0]) and (lst[1] is None or torch.equal(lst[1], self._lst[1]))):
+                self.rebuilds += 1
+            self._lst = lst
+            self._step.set_list(*lst)
+            self._post(*self._step.model())
+
+    def _stuck(self):
+        """The sticky word is set and it was not the driver's own doing (``_guarded`` raises then).  Host list: the list is stale,
+        repair it.  Device list: nothing is verified, repaired or re-recorded; it is the overflow guard of gn_padded_tail."""
+        if self.rebuild == "device":
+            raise RuntimeError(f"the neighbour search found {self.edge_count} edges, outside the padded layout's bound "
+                               f"[{self.N}, {self._step.layout.e_bound}]: the run stops at step {self._done}")
+        self._repair()
+
     @torch.no_grad()
     def run(self, n: int):
-        """Advance ``n`` steps.  Captured: the host reads the device state after every ``check_every`` replays, after the first
-        replay of a newly recorded graph and at the end (a stream synchronisation each)."""
-        if self.rebuild == "device":
-            return self._run_device(int(n))
-        if not self.captured:
-            for _ in range(int(n)):
-                self._pre(self._pos, self._cell)
-                self._after_pre()
-                lst = self._list(self._pos)
-                if not (torch.equal(lst[0], self._lst[0]) and (lst[1] is None or torch.equal(lst[1], self._lst[1]))):
-                    self.rebuilds += 1
-                self._lst = lst
-                self._eager.set_list(*lst)
-                self._post(*self._eager._body())
-                self._done += 1
-                if self._looked():
-                    break
-            return self
+        """Advance ``n`` steps.  The host reads the device state -- the sticky word, the step counter, then ``_looked`` -- after
+        every ``check_every`` steps, after the first replay of a newly recorded graph and at the end (a stream synchronisation
+        each).  Host list, eager: the search reads its edge count in every step anyway and the sticky word is the driver's own
+        business (``_after_pre``), so the steps are counted on the host and the state is not read."""
         target = self._done + int(n)
+        polled = self.captured or self.rebuild == "device"
         while self._done < target:
-            burst = 1 if self._fresh else min(self.check_every, target - self._done)
+            burst = 1 if self._fresh or not polled else min(self.check_every, target - self._done)
             for _ in range(burst):
-                self._step.graph.replay()
+                self._advance()
             self._fresh = False
-            stale, self._done = self._state.tolist()             # (the synchronisation)
-            if stale:
-                self._guarded()
-                self._repair()
-            if self._looked():
-                break
-        return self
-
-    def _run_device(self, n: int):
-        """``rebuild="device"``: nothing is verified, repaired or re-recorded.  The host reads the device state after every
-        ``check_every`` steps (after the first replay of the graph, and at the end) for the step counter, ``_looked`` and the
-        sticky word: a driver's own reasons (``_guarded``: the barostat's) raise first, else it is the overflow guard of
-        gn_padded_tail."""
-        target = self._done + n
-        while self._done < target:
-            burst = 1 if self._fresh else min(self.check_every, target - self._done)
-            for _ in range(burst):
-                if self.captured:
-                    self._step.graph.replay()
-                else:
-                    self._step._body()
-            self._fresh = False
-            overflow, self._done = self._state.tolist()          # (the synchronisation)
-            if overflow:
-                self._guarded()                                  # (a driver's own reasons first: they raise)
-                raise RuntimeError(f"the neighbour search found {self.edge_count} edges, outside the padded layout's bound "
-                                   f"[{self.N}, {self._step.layout.e_bound}]: the run stops at step {self._done}")
+            if polled:
+                stuck, self._done = self._state.tolist()         # (the synchronisation)
+                if stuck:
+                    self._guarded()                              # (a driver's own reasons first: they raise, or steer the repair)
+                    self._stuck()
+            else:
+                self._done += 1
             if self._looked():
                 break
         return self
@@ -424,14 +424,33 @@ class _ListDriver(metaclass=_RebuildOption):
     @property
     def edge_count(self) -> int:
         """The real edges of the current neighbour list (device mode: one host read of the device word)."""
-        if self.rebuild == "device":
-            return int(self._step.edge_count.item())
-        return self._step.g.E if self.captured else self._lst[0].shape[1]
+        return int(self._step.edge_count.item()) if self.rebuild == "device" else self._step.g.E
 
     def _ring(self, log):
         k = min(self.step, self.log_len)
         rows = [(s % self.log_len) for s in range(self.step - k, self.step)]
         return log[torch.tensor(rows, dtype=torch.long, device=log.device)]
+
+    # ---- state and queries -----------------------------------------------------------------------------------------
+    @property
+    def pos(self) -> torch.Tensor:
+        return self._pos.clone()
+
+    @property
+    def vel(self) -> torch.Tensor:
+        return self._vel.clone()
+
+    @property
+    def potential_energy(self) -> torch.Tensor:
+        """[n_mol], of the last completed step (of the start before the first)."""
+        return self._e.clone()
+
+    @property
+    def stress(self) -> torch.Tensor:
+        """[n_mol, 3, 3] of the last completed step (periodic runs: ``EnergyForces``' stress)."""
+        if self._stress is None:
+            raise ValueError("stress: this run has no cell")
+        return self._stress.clone()
 
 
 class MDRun(_ListDriver):
@@ -486,18 +505,14 @@ class MDRun(_ListDriver):
                                  log_len, rebuild=self.rebuild, barostat=barostat)
         dev = pos.device
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-        self._setup(ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured)
-        self.dt, self.force_scale, self.log_len = float(dt), float(force_scale), int(log_len)
+        self._setup(ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured, log_len, vel=vel)
+        self.dt, self.force_scale = float(dt), float(force_scale)
         self._mass = table.to(dev)
         self._thermo = None
         if thermostat is not None:
             c1, c2 = langevin_coefficients(thermostat["kT"], thermostat["gamma"], 0.5 * self.dt, self.force_scale)
             self._thermo = (c1, c2, torch.tensor(_key_words(thermostat["key"]), dtype=torch.int64, device=dev))
-        self._vel = torch.zeros((self.N, 3), **f32) if vel is None else vel.detach().to(**f32).clone().contiguous()
-        self._f = torch.empty((self.N, 3), **f32)                 # forces of the last completed step: the next kick's
-        self._e, self._ke = torch.empty(self.n_mol, **f32), torch.empty(self.n_mol, **f32)
-        self._stress = torch.empty((self.n_mol, 3, 3), **f32) if cell is not None else None
-        self._log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
+        self._ke = torch.empty(self.n_mol, **f32)
         self._baro = None
         if barostat is not None:
             self._baro = b = barostat_parameters(barostat, thermostat, cell)
@@ -507,11 +522,7 @@ class MDRun(_ListDriver):
             self._s, self._inv_s = torch.ones(self.n_mol, **f32), torch.ones(self.n_mol, **f32)
             self._reason = torch.zeros(self.n_mol, **i32)      # why a box set the sticky word: 1 cell guard, 2 max_step
             self._npt_log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
-        out = self._start(pos.detach().to(**f32).contiguous())
-        self._f.copy_(out[1])
-        self._e.copy_(out[0].reshape(-1))
-        if self._stress is not None:
-            self._stress.copy_(out[2])
+        self._start(pos.detach().to(**f32).contiguous())
         self._kinetic()
         if self._baro is not None:
             graph.cell_prepare(self._cell, self._inv_cell, self._volume)
@@ -588,14 +599,10 @@ class MDRun(_ListDriver):
             self._guarded()
             self._state[:1].zero_()
 
-    # ---- state and queries -----------------------------------------------------------------------------------------
+    # ---- state and queries (``pos``, ``vel``, ``potential_energy``, ``stress``: ``_ListDriver``'s) -----------------------------
     @property
-    def pos(self) -> torch.Tensor:
-        return self._pos.clone()
-
-    @property
-    def vel(self) -> torch.Tensor:
-        return self._vel.clone()
+    def _cell_moves(self) -> bool:
+        return self._baro is not None
 
     @property
     def step(self) -> int:
@@ -603,21 +610,9 @@ class MDRun(_ListDriver):
         return self._done
 
     @property
-    def potential_energy(self) -> torch.Tensor:
-        """[n_mol], of the last completed step (of the start before the first)."""
-        return self._e.clone()
-
-    @property
     def kinetic_energy(self) -> torch.Tensor:
         """[n_mol]: (1/2) sum m v^2 / force_scale, in the model's energy unit."""
         return self._ke.clone()
-
-    @property
-    def stress(self) -> torch.Tensor:
-        """[n_mol, 3, 3] of the last completed step (periodic runs: ``EnergyForces``' stress)."""
-        if self._stress is None:
-            raise ValueError("stress: this run has no cell")
-        return self._stress.clone()
 
     @property
     def cell(self) -> torch.Tensor:

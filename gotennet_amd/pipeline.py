@@ -6,7 +6,8 @@ reference-style callers (GotenModel / torch.autograd.grad).
 
 ``CapturedStep`` records that step on a fixed edge list into one hipGraph; ``RebuiltStep`` records it behind a rebuild of
 the list on the device, for a fixed cell or (``cell_moves=True``) for one that moves between the replays, its image ranges
-recomputed inside the chain by gn_cell_image_ranges."""
+recomputed inside the chain by gn_cell_image_ranges.  The chain itself is stated once (``energy_forces``), and so is the recording
+(``_record``): each class adds only what is its own in front of them."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -17,6 +18,36 @@ from . import engine, graph
 from ._lib import call, ptr
 from .gotennet import GotenNet
 from .outputs import Atomwise, molecule_ptr
+
+
+def energy_forces(cfg, pw, head, z32, g, mol_ptr, n_mol, volume=None):
+    """The energy-and-force chain, stated once for every step class and driver: forward (with tape) -> ``head.energy_raw`` ->
+    ``head.grad_h_raw`` -> backward -> force scatter, and gn_virial when ``volume`` (fp32 [n_mol], gn_cell_prepare's) is given.
+    ``g``: the ``engine.Graph`` with its geometry set.  -> (energy, forces) or (energy, forces, stress)."""
+    h, X, tape = engine.forward(cfg, pw, z32, g, save=True)
+    e, y, pre1 = head.energy_raw(h, z32, mol_ptr, n_mol, mode=cfg.gemm_mode)
+    gh = head.grad_h_raw(pre1, cfg.F_model or cfg.F, mode=cfg.gemm_mode)
+    g_vec, g_diff = engine.backward(cfg, pw, z32, g, tape, gh, None)
+    f = engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
+    if volume is None:
+        return e, f
+    return e, f, engine.virial(g, g_vec, g_diff, mol_ptr, n_mol, volume)
+
+
+def _record(body, device, warmup):
+    """``warmup`` runs of ``body`` on a side stream (weight planes / transposes are built there, off the capture), then one run
+    recorded into a ``torch.cuda.CUDAGraph`` (hipGraph on ROCm) on the default memory pool -> (graph, what that run returned:
+    the static output buffers of every replay)."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side), torch.no_grad():
+        for _ in range(warmup):
+            body()
+    torch.cuda.current_stream(device).wait_stream(side)
+    recorded = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(recorded), torch.no_grad():
+        out = body()
+    return recorded, out
 
 
 class EnergyForces:
@@ -103,8 +134,7 @@ class EnergyForces:
         ``cell``.  A call with ``cell`` neither uses nor creates the recorded step of ``replay=True``: it runs eagerly (a
         periodic MD loop records its step with ``CapturedStep(..., cell=, edge_shift=)``), and it leaves the count of consecutive calls that
         decides when a call without ``cell`` records (``replay_after``) where it was."""
-        if cell is not None and cell.requires_grad:                # before any launch
-            raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
+        graph.check_periodic_args(cell)                            # before any launch
         rep = self.rep
         cfg, pw = rep.config(), rep.packed_weights()
         N = z.shape[0]
@@ -138,16 +168,11 @@ class EnergyForces:
         return self._step(cfg, pw, g, z32, mol_ptr, n_mol, forces)
 
     def _step(self, cfg, pw, g, z32, mol_ptr, n_mol, forces, volume=None, periodic=False):
-        h, X, tape = engine.forward(cfg, pw, z32, g, save=forces)
-        e, y, pre1 = self.head.energy_raw(h, z32, mol_ptr, n_mol, mode=cfg.gemm_mode)
-        if not forces:
-            return (e, None, None) if periodic else (e, None)
-        gh = self.head.grad_h_raw(pre1, cfg.F_model or cfg.F, mode=cfg.gemm_mode)
-        g_vec, g_diff = engine.backward(cfg, pw, z32, g, tape, gh, None)
-        f = engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
-        if not periodic:
-            return e, f
-        return e, f, engine.virial(g, g_vec, g_diff, mol_ptr, n_mol, volume)
+        if forces:                                   # (a periodic call with forces always brings its volume)
+            return energy_forces(cfg, pw, self.head, z32, g, mol_ptr, n_mol, volume)
+        h, X, tape = engine.forward(cfg, pw, z32, g, save=False)
+        e = self.head.energy_raw(h, z32, mol_ptr, n_mol, mode=cfg.gemm_mode)[0]
+        return (e, None, None) if periodic else (e, None)
 
     # ---- hipGraph replay of the eager step on a cached topology --------------------------------------------------
     def _replay_ok(self, gs, cfg, pw, N, edge_index, n_mol) -> bool:
@@ -179,14 +204,7 @@ class EnergyForces:
             g.set_geometry(st["ed"], st["ev"])
             return self._step(cfg, pw, g, st["z32"], st["mol_ptr"], n_mol, True)
 
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                  # one run off the capture: weight planes / transposes are built here
-            body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        st["graph"] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(st["graph"]):
-            st["e"], st["f"] = body()
+        st["graph"], (st["e"], st["f"]) = _record(body, dev, 1)
         self._graph_state = st
         return st
 
@@ -306,7 +324,21 @@ class InFlight:
             ef.clear_cache()
 
 
-class CapturedStep:
+class _StepOutputs:
+    """What ``CapturedStep`` and ``RebuiltStep`` share: the kept outputs of ``_body`` -- the static buffers a recording writes
+    in every replay -- and what a call returns.  ``self.cell`` is None for a step without a cell."""
+
+    def _keep(self, out):
+        self.energy, self.forces = out[0], out[1]
+        self.stress = out[2] if self.cell is not None else None
+
+    def _outputs(self):
+        if self.cell is None:
+            return self.energy, self.forces
+        return self.energy, self.forces, self.stress
+
+
+class CapturedStep(_StepOutputs):
     """Energy + forces for a FIXED edge list (static topology: an MD trajectory of molecules whose neighbour lists do
     not change, e.g. any molecule smaller than the cutoff) as ONE hipGraph replay per step.
 
@@ -344,13 +376,9 @@ class CapturedStep:
         if (cell is None) != (edge_shift is None):           # before any launch
             raise ValueError("CapturedStep: a periodic step needs both cell and edge_shift (graph.distance_pbc returns the "
                              "shifts); neither for isolated molecules")
-        if cell is not None and cell.requires_grad:
-            raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
+        graph.check_periodic_args(cell, images)
         rep, head = ef.rep, ef.head
-        self.check_cell = bool(check_cell)
-        if images not in graph.IMAGE_MODES:
-            raise ValueError(f"images must be one of {graph.IMAGE_MODES}, got {images!r}")
-        self.images = images
+        self.check_cell, self.images = bool(check_cell), images
         if cell is not None and self.check_cell:
             graph.resolve_images(cell, float(rep.cutoff), images)
         self.cfg, self.pw = rep.config(), rep.packed_weights()
@@ -376,33 +404,14 @@ class CapturedStep:
             self.inv_cell, self.volume = torch.empty_like(self.cell), torch.empty(n_mol, dtype=torch.float32, device=dev)
             self.g.set_periodic(edge_shift.to(dev), batch.to(dev), self.cell)
         self.g.csc()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), torch.no_grad():                             # warm-up off the capture
-            for _ in range(max(1, warmup)):
-                self._body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph), torch.no_grad():
-            out = self._body()
-        self.energy, self.forces = out[0], out[1]
-        self.stress = out[2] if self.cell is not None else None
+        self.graph, out = _record(self._body, dev, max(1, warmup))
+        self._keep(out)
 
     def _body(self):
-        cfg, pw, g = self.cfg, self.pw, self.g
         if self.cell is not None:
             graph.cell_prepare(self.cell, self.inv_cell, self.volume)
-            g.set_positions(self.pos, self.cell)
-        else:
-            g.set_positions(self.pos)
-        h, X, tape = engine.forward(cfg, pw, self.z32, g, save=True)
-        e, y, pre1 = self.head.energy_raw(h, self.z32, self.mol_ptr, self.n_mol, mode=cfg.gemm_mode)
-        gh = self.head.grad_h_raw(pre1, cfg.F_model or cfg.F, mode=cfg.gemm_mode)
-        g_vec, g_diff = engine.backward(cfg, pw, self.z32, g, tape, gh, None)
-        f = engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
-        if self.cell is None:
-            return e, f
-        return e, f, engine.virial(g, g_vec, g_diff, self.mol_ptr, self.n_mol, self.volume)
+        self.g.set_positions(self.pos, self.cell)
+        return energy_forces(self.cfg, self.pw, self.head, self.z32, self.g, self.mol_ptr, self.n_mol, self.volume)
 
     @torch.no_grad()
     def __call__(self, pos: torch.Tensor, cell: Optional[torch.Tensor] = None):
@@ -417,12 +426,10 @@ class CapturedStep:
             self.cell.copy_(graph.broadcast_cell(cell.to(self.cell.device), self.n_mol))
         self.pos.copy_(pos)
         self.graph.replay()
-        if self.cell is None:
-            return self.energy, self.forces
-        return self.energy, self.forces, self.stress
+        return self._outputs()
 
 
-class RebuiltStep:
+class RebuiltStep(_StepOutputs):
     """Energy + forces with the neighbour list REBUILT inside the step: ``CapturedStep``'s counterpart for lists that change
     (liquids, hot molecules), still ONE hipGraph replay per step and no host read.
 
@@ -463,10 +470,7 @@ class RebuiltStep:
                  cell: Optional[torch.Tensor] = None, images: str = "minimum", warmup: int = 2, capture: bool = True,
                  state: Optional[torch.Tensor] = None, cell_moves: bool = False, reason: Optional[torch.Tensor] = None):
         rep, head = ef.rep, ef.head
-        if cell is not None and cell.requires_grad:          # before any launch
-            raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
-        if images not in graph.IMAGE_MODES:
-            raise ValueError(f"images must be one of {graph.IMAGE_MODES}, got {images!r}")
+        graph.check_periodic_args(cell, images)              # before any launch
         self.cell_moves = bool(cell_moves)
         if self.cell_moves and cell is None:
             raise ValueError("RebuiltStep: cell_moves=True needs a cell")
@@ -504,22 +508,9 @@ class RebuiltStep:
         self.reason = (torch.zeros(self.n_mol, **i32) if reason is None else reason) if self.cell_moves else None
         self.g = engine.Graph(self.cfg, self.pw, lay.n_atoms, self.edge_index, self_images=cell is not None)
         self.energy = self.forces = self.stress = self.graph = None
-        if not capture:
-            return
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), torch.no_grad():                             # warm-up off the capture
-            for _ in range(max(1, warmup)):
-                self._body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph), torch.no_grad():
-            out = self._body()
-        self._keep(out)
-
-    def _keep(self, out):
-        self.energy, self.forces = out[0], out[1]
-        self.stress = out[2] if self.cell is not None else None
+        if capture:
+            self.graph, out = _record(self._body, dev, max(1, warmup))
+            self._keep(out)
 
     def rebuild(self):
         """Steps 1 to 5 of the chain: the list of ``self.pos`` into the capacity-sized buffers, and the graph's topology."""
@@ -533,31 +524,24 @@ class RebuiltStep:
         return RebuiltStep._body(self)
 
     def _body(self):
-        cfg, pw, g, n_all = self.cfg, self.pw, self.g, self.n_mol + 1
-        if self.cell_moves:        # the inverse and the ranges of the CURRENT cell, before the count reads them
+        if self.cell_moves:       # the inverse and the ranges of the CURRENT cell, before the count reads them
             graph.cell_prepare(self._cell_all, self.inv_cell, self.volume)
             call("gn_cell_image_ranges", ptr(self.cell), self.n_mol, self.cutoff, graph.MAX_IMAGE_RANGE, ptr(self._ranges),
                  ptr(self.state), ptr(self.reason), engine._stream())
         self.rebuild()
         if self.cell is not None and not self.cell_moves:
             graph.cell_prepare(self._cell_all, self.inv_cell, self.volume)
-        g.set_geometry(self.edge_diff, self.edge_vec)     # (the fill's unshifted() / shifted(): the bits set_positions would give)
-        h, X, tape = engine.forward(cfg, pw, self.z32, g, save=True)
-        e, y, pre1 = self.head.energy_raw(h, self.z32, self.mol_ptr, n_all, mode=cfg.gemm_mode)
-        gh = self.head.grad_h_raw(pre1, cfg.F_model or cfg.F, mode=cfg.gemm_mode)
-        g_vec, g_diff = engine.backward(cfg, pw, self.z32, g, tape, gh, None)
-        f = engine.pos_gradient(g, g_vec, g_diff, sign=-1.0)
-        if self.cell is None:
-            return e[:self.n_mol], f[:self.N]
-        return e[:self.n_mol], f[:self.N], engine.virial(g, g_vec, g_diff, self.mol_ptr, n_all, self.volume)[:self.n_mol]
+        self.g.set_geometry(self.edge_diff, self.edge_vec)     # (the fill's unshifted() / shifted(): the bits set_positions would give)
+        # the padded system: n_mol + 1 molecules, the dummy atoms behind the N real ones; what leaves is the real part
+        e, f, *stress = energy_forces(self.cfg, self.pw, self.head, self.z32, self.g, self.mol_ptr, self.n_mol + 1, self.volume)
+        return (e[:self.n_mol], f[:self.N], *(s[:self.n_mol] for s in stress))
 
     @torch.no_grad()
     def set_cell(self, cell: torch.Tensor) -> None:
         """``cell_moves=True``: copy a new cell (fp32 [n_mol, 3, 3] or [3, 3]) into the static buffer; the next call prepares it,
         recomputes its image ranges and searches in it.  Not checked on the host: a cell the range kernel refuses sets the
         sticky ``state`` word and ``reason`` of its box."""
-        if cell.requires_grad:                                # before any launch
-            raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
+        graph.check_periodic_args(cell)                       # before any launch
         if not self.cell_moves:
             raise ValueError("RebuiltStep.set_cell: this step was built for a fixed cell; pass cell_moves=True")
         self.cell.copy_(graph.broadcast_cell(cell.to(self.cell.device), self.n_mol))
@@ -573,6 +557,4 @@ class RebuiltStep:
             self.graph.replay()
         else:
             self._keep(self._body())
-        if self.cell is None:
-            return self.energy, self.forces
-        return self.energy, self.forces, self.stress
+        return self._outputs()

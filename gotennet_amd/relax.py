@@ -62,10 +62,7 @@ def validate(pos, N, fmax, dt, dt_max, max_step, n_min, f_inc, f_dec, alpha, f_a
         raise ValueError(f"fixed: a bool or uint8 mask of shape [{N}] is expected")
     if pos.requires_grad:
         raise ValueError("pos requires grad: the driver moves plain tensors")
-    if cell is not None and cell.requires_grad:
-        raise ValueError("cell requires grad: autograd with respect to the cell is not supported")
-    if images not in graph.IMAGE_MODES:
-        raise ValueError(f"images must be one of {graph.IMAGE_MODES}, got {images!r}")
+    graph.check_periodic_args(cell, images)
     return graph.resolve_images(cell, float(cutoff), images) if cell is not None else None
 
 
@@ -92,6 +89,8 @@ class Relax(_ListDriver):
     ``rebuilds`` stays 0 -- for relaxations whose list changes in most steps.
 
     ``run`` raises ``RuntimeError`` naming the molecule when a force is not finite; nothing of that molecule has moved.
+    ``vel`` are FIRE's velocities (unit masses).  ``forces``, ``potential_energy`` and ``stress`` are those of the last completed
+    step; of a frozen molecule, the values it was judged on.  The stress is reported only: the cell is fixed.
 
     Refused with ``ValueError`` before any launch: fmax < 0; dt, dt_max or max_step not positive and finite; dt > dt_max;
     f_inc < 1; f_dec or f_alpha outside (0, 1); alpha outside (0, 1]; n_min < 0; ``fixed`` of the wrong shape or dtype; ``pos`` or
@@ -106,27 +105,17 @@ class Relax(_ListDriver):
                           float(ef.rep.cutoff), images, check_every, log_len)
         dev = pos.device
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
-        self._setup(ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured)
+        self._setup(ef, z, pos, batch, n_mol, cell, ranges, images, max_num_neighbors, check_every, captured, log_len)
         self.fmax_target, self.dt, self.dt_max, self.max_step = float(fmax), float(dt), float(dt_max), float(max_step)
         self.n_min, self.f_inc, self.f_dec, self.alpha, self.f_alpha = int(n_min), float(f_inc), float(f_dec), float(alpha), float(f_alpha)
-        self.log_len = int(log_len)
         self._fixed = None if fixed is None else fixed.to(device=dev, dtype=torch.uint8).contiguous()
-        # every buffer of the recorded chain is initialised here, by torch, never inside the recording
-        self._vel = torch.zeros((self.N, 3), **f32)
+        # every buffer of the recorded chain is initialised here (or in ``_setup``), by torch, never inside the recording
         self._dt, self._alpha = torch.full((self.n_mol,), self.dt, **f32), torch.full((self.n_mol,), self.alpha, **f32)
         self._n_pos, self._status = torch.full((self.n_mol,), -1, **i32), torch.zeros(self.n_mol, **i32)
         self._converged_at = torch.full((self.n_mol,), -1, **i32)
         self._coef = torch.zeros((self.n_mol, 4), **f32)
-        self._f = torch.empty((self.N, 3), **f32)                 # forces of the last completed step: what plan judges
-        self._e = torch.empty(self.n_mol, **f32)
-        self._stress = torch.empty((self.n_mol, 3, 3), **f32) if cell is not None else None
-        self._log = torch.zeros((self.log_len, self.n_mol, 2), **f32)
         self._host_status = [0] * self.n_mol                      # as of the host's last look
-        out = self._start(pos.detach().to(**f32).contiguous())
-        self._f.copy_(out[1])
-        self._e.copy_(out[0].reshape(-1))
-        if self._stress is not None:
-            self._stress.copy_(out[2])
+        self._start(pos.detach().to(**f32).contiguous())          # (the kept forces: what plan judges)
 
     # ---- the pieces of a step: the same launches whether recorded or eager -----------------------------------------
     def _pre(self, pos, cell=None):
@@ -159,31 +148,11 @@ class Relax(_ListDriver):
         return super().run(n)
 
     # ---- state and queries -----------------------------------------------------------------------------------------
-    @property
-    def pos(self) -> torch.Tensor:
-        return self._pos.clone()
-
-    @property
-    def vel(self) -> torch.Tensor:
-        """[N, 3]: FIRE's velocities (unit masses)."""
-        return self._vel.clone()
-
+    # (``pos``, ``vel``, ``potential_energy`` and ``stress`` are ``_ListDriver``'s)
     @property
     def forces(self) -> torch.Tensor:
         """[N, 3]: of the last completed step; of a frozen molecule, the forces it was judged on."""
         return self._f.clone()
-
-    @property
-    def potential_energy(self) -> torch.Tensor:
-        """[n_mol], as ``forces``."""
-        return self._e.clone()
-
-    @property
-    def stress(self) -> torch.Tensor:
-        """[n_mol, 3, 3], as ``forces`` (periodic runs; reported only: the cell is fixed)."""
-        if self._stress is None:
-            raise ValueError("stress: this run has no cell")
-        return self._stress.clone()
 
     @property
     def fmax(self) -> torch.Tensor:
