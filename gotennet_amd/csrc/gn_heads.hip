@@ -237,6 +237,7 @@ extern "C" int gn_geb_context(const float* s, int lds, int n_sin, const float* v
                               float* ctx, int ldc, void* stream) {
     if (N < 0 || n_sin <= 0 || n_vout <= 0 || ldc < n_sin + n_vout || lds < n_sin || ldv < n_vout) return GN_ERR_BAD_ARG;
     if (N == 0) return GN_OK;
+    if (!s || !vmix || !ctx) return GN_ERR_BAD_ARG;
     const size_t tot = (size_t)N * ldc;
     hipLaunchKernelGGL(gn::geb_context_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        s, lds, n_sin, vmix, ldv, n_vout, N, ctx, ldc);
@@ -246,10 +247,11 @@ extern "C" int gn_geb_context(const float* s, int lds, int n_sin, const float* v
 
 extern "C" int gn_geb_gate(const float* x, int ldx, int n_sout, int n_vout, const float* vmix, int ldv, int w_off, int N,
                            int sact, float* s_out, int lds, float* v_out, int ldo, void* stream) {
-    if (N < 0 || n_sout <= 0 || n_vout <= 0 || ldx < n_sout + n_vout || lds < n_sout || ldo < n_vout ||
+    if (N < 0 || n_sout <= 0 || n_vout <= 0 || w_off < 0 || ldx < n_sout + n_vout || lds < n_sout || ldo < n_vout ||
         ldv < w_off + n_vout || sact < -1 || sact >= GN_ACT_COUNT)
         return GN_ERR_BAD_ARG;
     if (N == 0) return GN_OK;
+    if (!x || !vmix || !s_out || !v_out) return GN_ERR_BAD_ARG;
     const size_t tot = (size_t)N * (n_sout + 3 * n_vout);
     hipLaunchKernelGGL(gn::geb_gate_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        x, ldx, n_sout, n_vout, vmix, ldv, w_off, N, sact, s_out, lds, v_out, ldo);
@@ -262,6 +264,7 @@ extern "C" int gn_dipole_reduce(const float* mu, int ldm, const float* q, int ld
                                 float* y_vec, void* stream) {
     if (n_mol < 0 || ldm <= 0 || ldq <= 0 || !y) return GN_ERR_BAD_ARG;
     if (n_mol == 0) return GN_OK;
+    if (!mu || !q || !pos || !mol_ptr) return GN_ERR_BAD_ARG;      // (y_vec stays optional)
     hipLaunchKernelGGL(gn::dipole_reduce_kernel, dim3(n_mol), dim3(64), 0, (hipStream_t)stream,
                        mu, ldm, q, ldq, pos, mol_ptr, scale, shift, standardise, magnitude, y, y_vec);
     GN_LAUNCH_CHECK();
@@ -272,6 +275,7 @@ extern "C" int gn_ese_reduce(const float* x, const float* pos, const int* z, con
                              const int* mol_ptr, int n_mol, float* y, void* stream) {
     if (n_mol < 0 || n_mass <= 0 || !y) return GN_ERR_BAD_ARG;
     if (n_mol == 0) return GN_OK;
+    if (!x || !pos || !z || !mass || !mol_ptr) return GN_ERR_BAD_ARG;
     hipLaunchKernelGGL(gn::ese_reduce_kernel, dim3(n_mol), dim3(64), 0, (hipStream_t)stream,
                        x, pos, z, mass, n_mass, mol_ptr, y);
     GN_LAUNCH_CHECK();

@@ -509,6 +509,8 @@ extern "C" int gn_embedding_grad_images(const float* g_ctx, const float* feat, i
                                         int n_species, int N, int F, const float* edge_diff, float* work, float* dA_na,
                                         float* dA_nbr, void* stream) {
     if (N < 0 || F < 1 || n_species < 1 || ldf < 2 * F) return GN_ERR_BAD_ARG;
+    if (!sp_ptr || !dA_na || !dA_nbr) return GN_ERR_BAD_ARG;      // read and written at N = 0 too: plain stores of zeros
+    if (N > 0 && (!g_ctx || !feat || !cut || !dst || !colptr || !perm || !order || !work)) return GN_ERR_BAD_ARG;
     const hipStream_t st = (hipStream_t)stream;
     const long nf = (long)N * F, sf = (long)n_species * F;
     if (nf > 0) {

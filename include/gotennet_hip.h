@@ -472,18 +472,28 @@ int gn_head_grad(const float* pre1, const float* W2, float scale, const float* a
  *   vmix [N*3, ldv] = mix_vectors(vectors): V at column 0, W at column w_off, each n_vout wide;
  *   gn_geb_context:  ctx [N, ldc] = [scalars (n_sin) | ||V||_2 over the 3 components (n_vout) | zeros];
  *   x [N, ldx] = scalar_net(ctx) = [s (n_sout) | gate (n_vout) | padding]            (gn_gemm, twice);
- *   gn_geb_gate:     s_out = sactivation(s) (sact = GN_ACT_* or -1 for none), v_out [N*3, ldo] = gate * W. */
+ *   gn_geb_gate:     s_out = sactivation(s) (sact = GN_ACT_* or -1 for none), v_out [N*3, ldo] = gate * W.
+ * gn_geb_context writes every column of ctx (the padding [n_sin + n_vout, ldc) as 0: the product that follows reads
+ * whole rows); gn_geb_gate writes columns [0, n_sout) of s_out and [0, n_vout) of v_out and leaves the rest alone.
+ * GN_ERR_BAD_ARG before any launch: a width <= 0, a leading dimension below its width (ldc < n_sin + n_vout,
+ * ldx < n_sout + n_vout, ldv < w_off + n_vout), w_off < 0, an unknown sact, and -- once N > 0 -- a NULL pointer.
+ * N = 0: GN_OK, nothing read or written. */
 int gn_geb_context(const float* s, int lds, int n_sin, const float* vmix, int ldv, int n_vout, int N,
                    float* ctx, int ldc, void* stream);
 int gn_geb_gate(const float* x, int ldx, int n_sout, int n_vout, const float* vmix, int ldv, int w_off, int N,
                 int sact, float* s_out, int lds, float* v_out, int ldo, void* stream);
 /* Dipole (outputs.py:430-468): y_b = sum_{n in molecule b} (mu_n + pos_n q_n), q_n = scale q_n + shift when
- * standardise; y [n_mol,3], or [n_mol] = |y_b| when magnitude; y_vec [n_mol,3] = sum mu_n (or NULL). */
+ * standardise; y [n_mol,3], or [n_mol] = |y_b| when magnitude; y_vec [n_mol,3] = sum mu_n (or NULL).
+ * mu [N*3, ldm] and q [N, ldq]: column 0 is read.  An empty molecule gives zeros.  GN_ERR_BAD_ARG before any launch:
+ * n_mol < 0, ldm or ldq <= 0, y NULL, and -- once n_mol > 0 -- mu, q, pos or mol_ptr NULL.  n_mol = 0: GN_OK, nothing
+ * read or written. */
 int gn_dipole_reduce(const float* mu, int ldm, const float* q, int ldq, const float* pos, const int* mol_ptr,
                      int n_mol, float scale, float shift, int standardise, int magnitude, float* y, float* y_vec,
                      void* stream);
 /* ElectronicSpatialExtentV2 (outputs.py:516-545): c_b = mass-weighted centroid, y_b = sum_n |pos_n - c_b|^2 x_n;
- * mass [n_mass] indexed by atomic number. */
+ * mass [n_mass] indexed by atomic number (z < 0 or >= n_mass: mass 0).  A molecule whose masses sum to 0 (an empty one
+ * too) gets c_b = 0, no 0 / 0.  GN_ERR_BAD_ARG before any launch: n_mol < 0, n_mass <= 0, y NULL, and -- once
+ * n_mol > 0 -- x, pos, z, mass or mol_ptr NULL.  n_mol = 0: GN_OK, nothing read or written. */
 int gn_ese_reduce(const float* x, const float* pos, const int* z, const float* mass, int n_mass, const int* mol_ptr,
                   int n_mol, float* y, void* stream);
 /* Backward of the four kernels above (first-order training of the read-outs).  Node-local or one
@@ -770,7 +780,10 @@ int gn_weight_grad_group_mode(const gn_wgrad_desc* problems, int n, int mode, fl
  * dA_nbr[s] = sum over the non-self-loop edges e = (j -> i) with z_j = s of g_ctx[i, F:2F] feat[e, 0:F] cut[e]: first per
  * source atom j over the by-source view (colptr / perm of gn_build_csc, into work [N, F]), then per species.
  * order [N]: a stable argsort of z; sp_ptr [n_species + 1]: the first sorted position of each species (host plumbing).
- * Species without atoms get zero rows. */
+ * Species without atoms get zero rows, sources without out-edges zero rows of work.  dA_na and dA_nbr are plain
+ * stores, not accumulations: N = 0 still writes both as zeros (sp_ptr is read).  GN_ERR_BAD_ARG before any launch:
+ * N < 0, F < 1, n_species < 1, ldf < 2 F, sp_ptr, dA_na or dA_nbr NULL, and -- once N > 0 -- any other pointer NULL
+ * (edge_diff of the _images variant stays optional: NULL = every src == dst edge is a self-loop). */
 int gn_embedding_grad(const float* g_ctx, const float* feat, int ldf, const float* cut, const int* dst,
                       const int* colptr, const int* perm, const int* order, const int* sp_ptr, int n_species,
                       int N, int F, float* work, float* dA_na, float* dA_nbr, void* stream);
