@@ -10,8 +10,9 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    """``gotennet_amd.Relax`` (relax.py), imported on first use: the package itself loads what it loaded before."""
-    if name == "Relax":
-        from .relax import Relax
-        return Relax
+    """``gotennet_amd.Relax`` and ``gotennet_amd.CellRelax`` (relax.py), imported on first use: the package itself loads what
+    it loaded before."""
+    if name in ("Relax", "CellRelax"):
+        from . import relax
+        return getattr(relax, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -141,6 +141,8 @@ SIGNATURES = {
     "gn_fire_plan": [_P, _P, _P, _P, _I, _I, _D, _D, _I, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "gn_fire_move": [_P, _P, _P, _P, _P, _I, _I, _P, _D, _P, _P],
     "gn_fire_finish": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
+    "gn_cellrelax_forces": [_P, _P, _P, _P, _P, _D, _I, _P, _P, _P, _I, _I, _P, _P, _P],
+    "gn_cellrelax_apply": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "gn_weight_grad_workspace": [_P, _I],
     "gn_weight_grad_group": [_P, _I, _P, _L, _P],
     "gn_weight_grad_workspace_mode": [_P, _I, _I],

@@ -743,6 +743,29 @@ int gn_fire_finish(int* state, const int* status, const int64_t* batch, const fl
                    const float* energy, float* energy_keep, const float* stress, float* stress_keep, int n_mol,
                    void* stream);
 
+/* ---- variable-cell relaxation: FIRE over the atoms and the cell of every periodic box (gotennet_amd/relax.py, CellRelax;
+ * ASE's UnitCellFilter for row vectors) ---------------------------------------------------------------------------------
+ * Per box m: the reference cell cell0[m] (the start), the deformation gradient F, the reference coordinates x~;
+ * pos = x~ F, cell = cell0 F.  The extended arrays x_ext / g_ext fp32 [N + 3 n_mol, 3] hold, for box m, rows
+ * [mol_ptr[m] + 3 m, mol_ptr[m + 1] + 3 (m + 1)): its atom rows (x~; the generalised forces on them), then three cell rows
+ * (U = weight[m] F; the generalised forces G on them), so gn_fire_plan and gn_fire_move run on them with
+ * mol_ptr_ext[m] = mol_ptr[m] + 3 m as on molecules of n_m + 3 atoms.  mol_ptr int32 [n_mol + 1] is the REAL one; every index
+ * derived from it is clamped to [0, N].  weight fp32 [n_mol] > 0.  One workgroup of 256 threads per box, fp64 from the fp32
+ * inputs, every stored value rounded once, plain stores in a fixed order: identical inputs give identical bits.  `state` is
+ * the pair above: both read state[0] first and do NOTHING when it is set. */
+/* g_ext of the kept force [N, 3] and stress [n_mol, 9] (sigma = (1/V) sum r (x) dE/dr, not symmetrised) at the current cell
+ * [n_mol, 9], F = cell rows of x_ext / weight:  atom rows g_ai = sum_j F_ij f_aj (0 for an atom of fixed uint8 [N], NULL:
+ * none);  cell rows G = -(V / weight) F^-T S with V = |det cell| and S = (sigma + sigma^T) / 2 + pressure I, with
+ * hydrostatic != 0 S <- (tr S / 3) I, and then exactly 0 where cell_mask uint8 [9] (NULL: all ones) is 0.  That is
+ * -dH/d(x~, U) of H = E + pressure V.  A stress that is not finite gives cell rows that are not finite. */
+int gn_cellrelax_forces(const float* force, const float* stress, const float* cell, const float* x_ext, const float* weight,
+                        double pressure, int hydrostatic, const unsigned char* cell_mask, const unsigned char* fixed,
+                        const int* mol_ptr, int N, int n_mol, float* g_ext, const int* state, void* stream);
+/* Behind gn_fire_move on x_ext: a box with coef[m][3] == 1 (gn_fire_plan's) reads F from its moved cell rows and writes
+ * pos = x~ F for every one of its atoms, fixed ones included, and cell[m] = cell0[m] F; any other box writes nothing. */
+int gn_cellrelax_apply(const float* x_ext, const float* cell0, const float* weight, const float* coef, const int* mol_ptr,
+                       int N, int n_mol, float* pos, float* cell, const int* state, void* stream);
+
 /* ---- parameter gradients (first-order training: a loss on energies and / or (h, X)) -------------
  * Every reduction below runs in a fixed order and uses no atomics: identical inputs give identical bits. */
 /* dW = dY^T A and db = sum_r dY of a Dense product y = A W^T + b (layers.py:457-529): several independent problems in
