@@ -21,6 +21,47 @@ __device__ __forceinline__ void reduce_rows(float4 (&acc)[ROWS], float* red, int
     }
 }
 
+// ---- K6 pieces shared by message_aggregate_kernel, message_aggregate_group_kernel (gn_gata.hip) and, the first two,
+// hl_msg_fwd_kernel
+// attention head of the lane's four channels (from c0) in block b of the M-block value vector, per_head = M F / H
+__device__ __forceinline__ int block_head(int b, int F, int c0, int per_head) { return (b * F + c0) / per_head; }
+// gate of value block b for one edge (gotennet.py:516-529): (t_filter * x_j) * cutoff + a[head] * v_j; tr / xr / vr: the
+// lane's channels of the edge's t_filter row and the source's x / v rows, ar: the edge's attention row
+__device__ __forceinline__ float4 msg_gate(const float* tr, const float* xr, const float* vr, const float* ar, float ce, int b, int F, int head) {
+    const float4 sp = (ld4_nt(tr + b * F) * ld4(xr + b * F)) * ce;
+    const float ab = ar[head];
+    return fma4(ab, ld4(vr + b * F), sp);
+}
+// residual-add epilogue: h_out[i] = h_in[i] + s;  X_out[i, m] = X_in[i, m] + s, or s alone where X_in is identically zero
+__device__ __forceinline__ void add_h_row(float* h_out, const float* h_in, int i, int F, int c0, float4 s) {
+    st4(h_out + (size_t)i * F + c0, ld4(h_in + (size_t)i * F + c0) + s);
+}
+template <bool ZERO_X = false>
+__device__ __forceinline__ void add_X_row(float* X_out, const float* X_in, int i, int D, int m, int F, int c0, float4 s) {
+    const size_t off = ((size_t)i * D + m) * F + c0;
+    if constexpr (ZERO_X) st4(X_out + off, s);
+    else st4(X_out + off, ld4(X_in + off) + s);
+}
+
+// ---- K7: closed form of one HTR block B (a degree, or all D rows when joint) with rejection on,
+//   w_B = EQ.EK - (2 - r.r)(EQ.r)(EK.r)
+// (the two vector rejections of gotennet.py:351-364, 586-599: P(a) = a - (a.r) r, P'(b) = b - (b.(-r))(-r);
+//  P(a).P'(b) = a.b - 2 (a.r)(b.r) + (a.r)(b.r)(r.r)); r.r is not 1 for the reference's degree 3 (and 0 on self-loops), so
+// it is carried.  row() accumulates one row of the block, ab alone is the block without rejection.
+// w() spells it ab + (pq pk)(rr - 2): rr - 2 = -(2 - rr) and x (-y) = -(x y) are exact in IEEE arithmetic, so these are the
+// bits of ab - (pq pk)(2 - rr); written the other way round htr_edge_kernel<3, *> came out with 127 / 128 VGPRs for 126.
+struct HtrBlock {
+    float4 pq = zero4(), pk = zero4(), ab = zero4();
+    float rr = 0.f;
+    __device__ __forceinline__ void row(float r, float4 eq, float4 ek) {
+        rr = fmaf(r, r, rr);
+        pq = fma4(r, eq, pq);
+        pk = fma4(r, ek, pk);
+        ab = fma4(eq, ek, ab);
+    }
+    __device__ __forceinline__ float4 w() const { return ab + (pq * pk) * (rr - 2.0f); }
+};
+
 struct MsgBwdArgs {
     // saved forward tensors
     const float* x; const float* v; int ldxv;          // [N, M F]

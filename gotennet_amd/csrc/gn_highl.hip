@@ -10,7 +10,8 @@
 //   * lmax, sep_dir, sep_tensor and the HTR mode bits are runtime values: 9 + 8 + 8 + 8 + 4 kernels cover every
 //     (lmax, flag) combination, where templates over (LMAX, flags, group) would need a few hundred.
 // The per-row arithmetic is the tuned kernels' (same expressions, same order inside a row), so at lmax <= 4 the
-// message outputs are bit-identical to theirs (tests/test_hip_highl.py runs both with GN_FORCE_HIGHL=1).
+// message outputs are bit-identical to theirs (tests/test_hip_highl.py runs both: GN_LMAX_SLICED in the lmax argument
+// of a call selects this family at lmax <= 4).
 // Speed is not the point here -- nobody benchmarks l > 4 -- correctness and coverage are.
 //
 // Forward equations: gotennet.py:452-559 (message), 351-364 + 561-611 (HTR); backward as in gn_backward.hip.
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(256) void hl_msg_fwd_kernel(
     const int e0 = rowptr[i], e1 = rowptr[i + 1];
     const int D = S.D, per_head = (S.M * F) / H;
     const int bd = L == 0 ? 0 : S.dir_block(L), bt = L == 0 ? 0 : S.ten_block(L);
-    const int hd = (bd * F + c0) / per_head, ht = (bt * F + c0) / per_head;
+    const int hd = block_head(bd, F, c0, per_head), ht = block_head(bt, F, c0, per_head);
     const float NEG = -INFINITY;
 
     float4 acc[ROWS];
@@ -72,11 +73,7 @@ __global__ __launch_bounds__(256) void hl_msg_fwd_kernel(
         const float* vr = v + (size_t)j * ldxv + c0;
         const float* tr = tf + (size_t)e * ldt + c0;
         const float* ar = a + (size_t)e * H;
-        // gotennet.py:516-529: (t_filter * x_j) * cutoff + attn * v_j, block b of the value vector
-        auto gate = [&](int b, int hb) {
-            const float4 sp = (ld4_nt(tr + b * F) * ld4(xr + b * F)) * ce;
-            return fma4(ar[hb], ld4(vr + b * F), sp);
-        };
+        auto gate = [&](int b, int hb) { return msg_gate(tr, xr, vr, ar, ce, b, F, hb); };
         if constexpr (L == 0) {
             const float4 c = gate(0, hd);
             acc[0] = AGGR == 2 ? max4(acc[0], c) : acc[0] + c;
@@ -94,8 +91,8 @@ __global__ __launch_bounds__(256) void hl_msg_fwd_kernel(
     auto write = [&](int row, float4 s) {
         if constexpr (AGGR == 1) s = s * (1.0f / (float)(e1 > e0 ? e1 - e0 : 1));
         if constexpr (AGGR == 2) { if (e1 == e0) s = zero4(); }
-        if constexpr (L == 0) {
-            st4(h_out + (size_t)i * F + c0, ld4(h_in + (size_t)i * F + c0) + s);
+        if constexpr (L == 0) {                     // (add_h_row / add_X_row of gn_highl.h, written out: through them the nine
+            st4(h_out + (size_t)i * F + c0, ld4(h_in + (size_t)i * F + c0) + s);        // AGGR = 2 kernels compiled to other code)
         } else {
             const size_t off = ((size_t)i * D + (M0 + row)) * F + c0;
             st4(X_out + off, ld4(X_in + off) + s);
@@ -103,7 +100,7 @@ __global__ __launch_bounds__(256) void hl_msg_fwd_kernel(
     };
     if constexpr (AGGR != 2) {
         reduce_rows<ROWS>(acc, red, slot, c0, F, ns, write);
-    } else {                                         // the same fixed-order pass over the slots, with max for +
+    } else {     // the same fixed-order pass over the slots, with max for + (as a combine parameter of reduce_rows: <2, 2> 31.0 -> 35.5 us)
 #pragma unroll
         for (int base = 0; base < ROWS; base += CH) {
             if (base) __syncthreads();
@@ -382,7 +379,7 @@ __global__ __launch_bounds__(256) void hl_msg_bwd_source_X_kernel(const MsgBwdAr
 }
 
 // ------------------------------------------------------------------ HTR edge weights, all degrees and modes, one launch
-// per block B (a degree, or all D rows when `joint`):  w += A.B - (2 - r.r)(A.r)(B.r)  [rejection on];  w += A.B  [off]
+// per block B (a degree, or all D rows when `joint`):  w += HtrBlock::w() (gn_highl.h)  [rejection on];  w += A.B  [off]
 __global__ __launch_bounds__(256) void hl_htr_edge_kernel(
     const float* __restrict__ EQ, const float* __restrict__ EK, const float* __restrict__ rl,
     const int* __restrict__ rowptr, const int* __restrict__ src, int N, int F, int lmax, int joint, int rej, int gate,
@@ -397,23 +394,17 @@ __global__ __launch_bounds__(256) void hl_htr_edge_kernel(
     for (int e = e0 + slot; e < e1; e += ns) {
         const float* kj = EK + (size_t)src[e] * D * F + c0;
         const float* re = rl + (size_t)e * D;
-        float4 wsum = zero4(), ab = zero4(), pa = zero4(), pb = zero4();
-        float rr = 0.f;
+        float4 wsum = zero4();
+        HtrBlock blk;
         int left = 3, l = 1;                         // rows left in the current degree
         for (int m = 0; m < D; ++m) {
-            const float4 eq = ld4(qi + (size_t)m * F), ek = ld4(kj + (size_t)m * F);
-            const float r = re[m];
-            ab = fma4(eq, ek, ab);
-            pa = fma4(r, eq, pa);
-            pb = fma4(r, ek, pb);
-            rr = fmaf(r, r, rr);
+            blk.row(re[m], ld4(qi + (size_t)m * F), ld4(kj + (size_t)m * F));
             if (--left == 0) {
                 ++l;
                 left = 2 * l + 1;
                 if (!joint || m == D - 1) {
-                    wsum = wsum + (rej ? ab - (pa * pb) * (2.0f - rr) : ab);
-                    ab = pa = pb = zero4();
-                    rr = 0.f;
+                    wsum = wsum + (rej ? blk.w() : blk.ab);
+                    blk = HtrBlock{};
                 }
             }
         }

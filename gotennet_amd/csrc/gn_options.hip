@@ -10,8 +10,6 @@
 
 namespace gn {
 
-
-
 // row m (0-based, l = 0 omitted) closes degree l when m + 2 = (l + 1)^2
 __host__ __device__ constexpr bool closes_degree(int m) {
     for (int l = 1; l <= 8; ++l)
@@ -25,10 +23,8 @@ __host__ __device__ constexpr int degree_of(int m) {
 }
 
 // ------------------------------------------------------------------ forward
-// per block B (a degree, or all D rows when `joint`):  w += A.B - (2 - r.r)(A.r)(B.r)   [rejection on]
-//                                                       w += A.B                        [rejection off]
-// (closed form of the two vector rejections at gotennet.py:351-364, 586-599: P(a) = a - (a.r) r,
-//  P'(b) = b - (b.(-r))(-r);  P(a).P'(b) = a.b - 2 (a.r)(b.r) + (a.r)(b.r)(r.r).)
+// per block B (a degree, or all D rows when `joint`):  w += HtrBlock::w(), the closed form of gn_highl.h   [rejection on]
+//                                                       w += A.B                                        [rejection off]
 template <int LMAX>
 __global__ __launch_bounds__(256) void htr_edge_general_kernel(
     const float* __restrict__ EQ, const float* __restrict__ EK, const float* __restrict__ rl,
@@ -46,20 +42,14 @@ __global__ __launch_bounds__(256) void htr_edge_general_kernel(
     for (int e = e0 + slot; e < e1; e += ns) {
         const float* kj = EK + (size_t)src[e] * D * F + c0;
         const float* re = rl + (size_t)e * D;
-        float4 wsum = zero4(), ab = zero4(), pa = zero4(), pb = zero4();
-        float rr = 0.f;
+        float4 wsum = zero4();
+        HtrBlock blk;
 #pragma unroll
         for (int m = 0; m < D; ++m) {
-            const float4 ek = ld4(kj + (size_t)m * F);
-            const float r = re[m];
-            ab = fma4(eq[m], ek, ab);
-            pa = fma4(r, eq[m], pa);
-            pb = fma4(r, ek, pb);
-            rr = fmaf(r, r, rr);
+            blk.row(re[m], eq[m], ld4(kj + (size_t)m * F));
             if (m == D - 1 || (closes_degree(m) && !joint)) {
-                wsum = wsum + (rej ? ab - (pa * pb) * (2.0f - rr) : ab);
-                ab = pa = pb = zero4();
-                rr = 0.f;
+                wsum = wsum + (rej ? blk.w() : blk.ab);
+                blk = HtrBlock{};
             }
         }
         if (w_raw) st4(w_raw + (size_t)e * F + c0, wsum);

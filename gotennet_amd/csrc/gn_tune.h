@@ -36,12 +36,9 @@
 #define GN_W_ATTN 0        // 2: 29 -> 55 us; 4: 37 us
 #endif
 
-#ifndef GN_K6_MERGE34
-#define GN_K6_MERGE34 1    // lmax = 4: degrees 3 and 4 of the message kernel in ONE launch (16 accumulator rows):
-#endif                     // C2 message stage 245.9 -> ~235 us (two launches: 60 + 64 us for 111 MB of t_filter each)
 #ifndef GN_W_K6_G34
-#define GN_W_K6_G34 2      // ... at 2 waves/SIMD (3: 275.6 us, spills; no hint: 325 us)
-#endif
+#define GN_W_K6_G34 2      // message_aggregate_group34_kernel (lmax 4, degrees 3 and 4 in one launch, 16 accumulator rows): 2 waves/SIMD
+#endif                     // (3: 275.6 us, spills; no hint: 325 us)
 // (lmax = 4 backward: the same {3,4} merge was measured for the four backward passes in round 2 and lost -- message
 // backward 676 -> 682 / 716 us per layer for the target / source pass, HTR backward 381 -> 413 / 423 us: 16 extra live
 // gradient rows cost more than the saved re-reads; the switches are gone, the passes run one degree per launch.)
@@ -132,13 +129,9 @@
 #define GN_F16_BIG8_PHASED 1     // that kernel: waves 4..7 split the next slab BEFORE they multiply the current one, waves 0..3 after (0: all after; 2: the odd waves
                                  // before).  Stand-alone [54368 x 256 x 1792], cold: 207.3 (0) / 200.2 (1) / 203.1 us (2), four-wave tile 216.9
 #endif
-#ifndef GN_HTR_CLOSED
-#define GN_HTR_CLOSED 1        // htr_edge_kernel at lmax = 3: closed form EQ.EK - (2 - r.r)(EQ.r)(EK.r) instead of two rejections
-#endif
-#ifndef GN_HTR_CLOSED_ALL
-#define GN_HTR_CLOSED_ALL 4    // ... and from this lmax up the closed form with EVERY row of the edge requested before the first use: lmax 4
-#endif                         // 108.4 -> 90 us per call (degree by degree the closed form lost there, 140 us: the compiler serialised the
-                               // row loads); lmax 3 is 90.4 us degree by degree, 92.4 us in this form (0: never)
+// (settled, the switches are gone and the findings stand at the sites they decide in gn_gata.hip: htr_edge_kernel runs the
+// closed form at lmax 3 degree by degree and at lmax 4 with every row of the edge requested first; the message kernel runs
+// degrees 3 and 4 of lmax 4 in one launch -- message_launch.)
 #ifndef GN_ATTN_WAVE
 #define GN_ATTN_WAVE 1         // 1: one wave per target in gn_attn_softmax where the shape allows; 0: workgroup per target
 #endif
