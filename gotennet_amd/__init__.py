@@ -10,9 +10,13 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    """``gotennet_amd.Relax`` and ``gotennet_amd.CellRelax`` (relax.py), imported on first use: the package itself loads what
-    it loaded before."""
+    """``gotennet_amd.Relax`` and ``gotennet_amd.CellRelax`` (relax.py) and ``gotennet_amd.NEB`` (neb.py), imported on first use:
+    the package itself loads what it loaded before."""
     if name in ("Relax", "CellRelax"):
         from . import relax
         return getattr(relax, name)
+    if name in ("NEB", "neb"):
+        import importlib
+        neb = importlib.import_module(".neb", __name__)
+        return neb if name == "neb" else neb.NEB
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -143,6 +143,8 @@ SIGNATURES = {
     "gn_fire_finish": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
     "gn_cellrelax_forces": [_P, _P, _P, _P, _P, _D, _I, _P, _P, _P, _I, _I, _P, _P, _P],
     "gn_cellrelax_apply": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "gn_neb_forces": [_P, _P, _P, _P, _P, _I, _I, _I, _D, _I, _P, _P, _P, _P, _P],
+    "gn_neb_finish": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P],
     "gn_weight_grad_workspace": [_P, _I],
     "gn_weight_grad_group": [_P, _I, _P, _L, _P],
     "gn_weight_grad_workspace_mode": [_P, _I, _I],

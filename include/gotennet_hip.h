@@ -766,6 +766,31 @@ int gn_cellrelax_forces(const float* force, const float* stress, const float* ce
 int gn_cellrelax_apply(const float* x_ext, const float* cell0, const float* weight, const float* coef, const int* mol_ptr,
                        int N, int n_mol, float* pos, float* cell, const int* state, void* stream);
 
+/* ---- nudged elastic band on the batched FIRE step (gotennet_amd/neb.py; improved tangent of Henkelman and Jonsson,
+ * J. Chem. Phys. 113, 9978) ---------------------------------------------------------------------------------------------
+ * Molecules b n_img .. (b + 1) n_img - 1 are the images of band b (n_img >= 3, n_mol a multiple of n_img); atom a of an
+ * image pairs with the atom at the same offset from mol_ptr in the two neighbouring images.  gn_fire_plan and gn_fire_move
+ * run unchanged on g_out with a band pointer (every n_img-th entry of mol_ptr) and per-band state.  `state` is the pair
+ * above: both entries read state[0] first and do NOTHING when it is set.  No atomics, fixed-order fp64 sums from the fp32
+ * inputs (products included), plain stores: identical inputs give identical bits. */
+/* g_out fp32 [N, 3] from the positions, the KEPT force [N, 3] and the KEPT energy [n_mol]; one workgroup of 256 per image.
+ * Interior image i, t+ = R_{i+1} - R_i, t- = R_i - R_{i-1}, the fp32 energies compared as they are:  E+ > E > E-: t = t+;
+ * E+ < E < E-: t = t-;  otherwise dmax / dmin = the larger / smaller of |E+ - E|, |E- - E| and t = dmax t+ + dmin t- when
+ * E+ > E-, else (ties included) t = dmin t+ + dmax t-.  All sums run over the free atoms (fixed uint8 [N], NULL: none).
+ * g = f - (f.t / |t|^2) t + k (|t+| - |t-|) t / |t|;  the climbing image (climb != 0: the interior image with the largest
+ * energy, the first of equal ones) gets g = f - 2 (f.t / |t|^2) t;  |t|^2 == 0: g = f;  one of the three energies not
+ * finite: g = NaN.  Rows of the two end images, of fixed atoms and of atoms beyond the shortest of the three images: 0.
+ * The workgroup of a band's first image writes e_band_out[b] (the largest energy of the band, a NaN wins) and climb_out[b]
+ * (the climbing image's index in the band, -1 when climb == 0).  k finite and >= 0. */
+int gn_neb_forces(const float* pos, const float* force, const float* energy, const unsigned char* fixed, const int* mol_ptr,
+                  int N, int n_mol, int n_img, double k, int climb, float* g_out, float* e_band_out, int* climb_out,
+                  const int* state, void* stream);
+/* gn_fire_finish with status int32 [n_mol / n_img] indexed per band: state[1] += 1, and force / energy / stress are copied
+ * into their *_keep buffers for the images m with status[m / n_img] == 0. */
+int gn_neb_finish(int* state, const int* status, const int64_t* batch, const float* force, float* force_keep, int N,
+                  const float* energy, float* energy_keep, const float* stress, float* stress_keep, int n_mol, int n_img,
+                  void* stream);
+
 /* ---- parameter gradients (first-order training: a loss on energies and / or (h, X)) -------------
  * Every reduction below runs in a fixed order and uses no atomics: identical inputs give identical bits. */
 /* dW = dY^T A and db = sum_r dY of a Dense product y = A W^T + b (layers.py:457-529): several independent problems in
